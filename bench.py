@@ -12,19 +12,33 @@ A "step" is ONE pass of the hot path over the whole resident batch: one `_game_m
 metric config: synthetic random-geometry trusses, 32 nodes / 80 elements / 60 DOF, FEM-only (no agent).  Inputs
 (design state, per-env constants, a pool of pre-drawn actions) are resident in HBM before the timed region starts.
 
-`value` is the path an AGENT CAN DRIVE: one launch of truss_step_kernel per step (`truss_step`; the K launches of a
+`value` is the path an AGENT CAN DRIVE: one launch of truss_step_kernel per step (`truss_step`; the launches of a
 timed block are issued back to back by the C entry `truss_rollout` in its one-launch-per-step mode, exactly what a
 replayed hipGraph of K `truss_step` calls does) -- the reference never chains steps with actions known up front
-(master_DDPG_truss2D_MO.py:249-260).  The persistent K-steps-in-one-launch kernel (`truss_rollout_kernel`) is reported
-next to it as `persistent_rollout`, the state-emitting step (`TRUSS_F_EMIT_OBS`, what configs[2]-[4] execute) as
-`state_emitting_step`, and a time-boxed `configs` object carries BASELINE configs[2]-[4] (bench_configs.py).
+(master_DDPG_truss2D_MO.py:249-260).
+
+A plain run (the driver's contract above) does only what that headline needs: set up, W warm-up steps, the K timed steps,
+the outputs of the last step with --dump-outputs DIR, the JSON line.  --full adds everything else this script measures:
+the persistent K-steps-in-one-launch kernel (`truss_rollout_kernel`) as `persistent_rollout`, the state-emitting step
+(`TRUSS_F_EMIT_OBS`, what configs[2]-[4] execute) as `state_emitting_step`, the numpy-oracle `cpu_baseline`, the strong-
+scaling legs of a multi-GPU weak run, and a time-boxed `configs` object with BASELINE configs[2]-[4] (bench_configs.py);
+--extras (implies --full) also times other topologies (bench_extras.py).
 
   --scaling weak    (default) 4096 envs PER GPU ("at 4096 envs" is the kernel's design point: one wave per SIMD)
   --scaling strong  --global-envs (default 4096; BASELINE configs[3] is 8192) split contiguously over the ranks
-With N > 1 the weak line also carries a "strong" object (4096 and 8192 global envs) measured by the same ranks.
+With N > 1 and --full the weak line also carries a "strong" object (4096 and 8192 global envs) measured by the same ranks.
 
-The K-step block is timed BLOCKS times (each bracketed by barrier + synchronize); `value` / `ms_per_step` are the
-median block, min / max are reported next to them.  Rank 0 prints ONE JSON line; DESIGN.md "Measurement".
+The K timed steps are split into up to BLOCKS consecutive blocks (timed_blocks), each bracketed by barrier + synchronize;
+`ms_per_step` / `value` are those of the median block (per step), min / max are reported next to them.  On the GPU a block
+has at least MIN_BLOCK_STEPS steps (one block for smaller K) and max(W, GPU_WARMUP_MIN) untimed steps run before the first
+(`warmup_steps_run`), so that the figure does not depend on K through launch latency or the clock ramp; the CPU rehearsal
+of the tests runs W warm-up steps and up to BLOCKS blocks of any size.  Rank 0 prints ONE JSON line;
+DESIGN.md "Measurement".
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step -- the arrays a caller of
+`BatchedTruss.rollout` receives (new heights / sections, displacements, member forces / stress ratios / compression flags,
+points, objectives, move limits, status) -- as DIR/<name>.npy in float32, rank r > 0 as DIR/<name>.rank<r>.npy.  The
+inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import hashlib
@@ -44,6 +58,8 @@ N_EXTRA = 4         # 76 reference elements + 4 long braces = 80
 N_ACTION_SETS = 8
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BLOCKS = 5
+MIN_BLOCK_STEPS = 10000   # on the GPU a timed block pays ~60 us of launch + synchronize latency: >= 10000 steps keep that < 0.05 %
+GPU_WARMUP_MIN = 4000     # untimed steps before the first timed one on the GPU (~75 ms at 4096 envs: the clocks ramp up under load)
 
 
 def algorithmic_bytes_per_env_step(N, E):
@@ -153,8 +169,52 @@ def spawn_ranks(n, argv):
     return rc
 
 
+def timed_blocks(steps, min_block=MIN_BLOCK_STEPS):
+    """the K timed steps as consecutive blocks of at least `min_block` steps (one block when K is smaller), at most BLOCKS of
+    them, whose sizes differ by at most one step"""
+    nb = max(1, min(BLOCKS, steps // min_block))
+    return [steps // nb + (1 if i < steps % nb else 0) for i in range(nb)]
+
+
+def measure_steps(env, G, T, steps, warmup, min_block, dist, distributed):
+    """The headline: exactly `steps` timed steps in timed_blocks(steps, min_block) -> (wall seconds per step of the median block (each block
+    max-over-ranks), min, max over blocks, device ms per step of the median block, number of blocks)."""
+    per, devs = [], []
+    for b, k in enumerate(timed_blocks(steps, min_block)):
+        el, dev_ms = distributed.timed_rollout(env, G, T, k, warmup if b == 0 else 0, dist)
+        per.append(el / k)
+        devs.append(dev_ms / k if dev_ms is not None else None)
+    med = sorted(range(len(per)), key=lambda i: per[i])[len(per) // 2]
+    return per[med], min(per), max(per), devs[med], len(per)
+
+
+DUMP_CAP_BYTES = 64 << 20
+DUMP_KEYS = ("y", "sec", "max_up", "max_down", "disp", "q0", "sr", "comp", "point", "obj", "status")
+
+
+def dump_outputs(env, path, rank, world):
+    """BatchedTruss.results() of the last timed step (the arrays truss_rollout writes) as float32 .npy files.  When a rank's share
+    of the 64 MB cap is smaller than its batch, a fixed sample of env rows (seed 0, sorted) is written, with its row indices as
+    env_index.npy.  Returns the names written."""
+    import numpy as np
+    res = env.results()
+    arrs = {k: np.asarray(res[k]) for k in DUMP_KEYS}
+    B = arrs["y"].shape[0]
+    per_env = sum(a[0].size * 4 for a in arrs.values()) + 8             # + its float64 row index when sampled
+    rows = max(1, (DUMP_CAP_BYTES // max(world, 1)) // per_env)
+    if B > rows:
+        idx = np.sort(np.random.default_rng(0).choice(B, rows, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64 if k == "env_index" else np.float32))
+    return sorted(arrs)
+
+
 def measure(env, G, T, steps, warmup, dist, distributed):
-    """BLOCKS timed K-step blocks -> (median, min, max wall seconds (each max-over-ranks), device ms of the median block)."""
+    """(--full legs) BLOCKS timed K-step blocks -> (median, min, max wall seconds (each max-over-ranks), device ms of the median block)."""
     walls, devs = [], []
     for b in range(BLOCKS):
         el, dev_ms = distributed.timed_rollout(env, G, T, steps, warmup if b == 0 else 0, dist)
@@ -226,12 +286,19 @@ def main():
     ap.add_argument("--envs", type=int, default=ENVS_PER_GPU, help="envs per GPU (weak scaling)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--global-envs", type=int, default=4096, help="total envs, split over the ranks (strong scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the time-boxed BASELINE configs[2]-[4] object")
-    ap.add_argument("--configs-budget", type=float, default=90.0, help="seconds the configs object may take")
-    ap.add_argument("--extras", action="store_true", help="also time the E=76 / small / large topologies (bench_extras.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the persistent rollout, the state-emitting step, the CPU baseline, the strong-scaling legs and the configs object")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the numpy-oracle CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) skip the time-boxed BASELINE configs[2]-[4] object")
+    ap.add_argument("--configs-budget", type=float, default=90.0, help="(--full) seconds the configs object may take")
+    ap.add_argument("--extras", action="store_true", help="--full, and also time the E=76 / small / large topologies (bench_extras.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--lib", default=None, help="diagnostic: another HIP build of the same ABI (default: the product library)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.full = args.full or args.extras
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))      # the parent has not imported torch: nothing here touched a GPU
@@ -243,7 +310,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
 
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline()                                 # forks: before the GPU is initialised
 
     import torch
@@ -284,12 +351,16 @@ def main():
     env, G, T, _ = distributed.make_rank_env(topo, B, rank, device=dev, lib=lib, seed=1234, n_action_sets=N_ACTION_SETS)
     # headline: ONE LAUNCH PER STEP (the path an agent can drive); every rank, barrier + max over ranks
     os.environ["TRUSS_ROLLOUT_LAUNCHES"] = "1"
-    elapsed, el_min, el_max, dev_ms = measure(env, G, T, args.steps, args.warmup, dist, distributed)
+    warm = max(args.warmup, GPU_WARMUP_MIN) if on_gpu else args.warmup
+    min_block = MIN_BLOCK_STEPS if on_gpu else 1
+    step_s, step_min, step_max, dev_ms_step, n_blocks = measure_steps(env, G, T, args.steps, warm, min_block, dist, distributed)
     del os.environ["TRUSS_ROLLOUT_LAUNCHES"]
     st = int(env.status.sum().item())
+    if args.dump_outputs:
+        dump_outputs(env, args.dump_outputs, rank, world)
     # the same K chained steps as ONE persistent launch (actions known up front: a bench / population-optimiser path)
     persistent = None
-    if bool(env.persistent_rollout):
+    if args.full and bool(env.persistent_rollout):
         w, wmin, wmax, d_ms = measure(env, G, T, args.steps, args.warmup, dist, distributed)
         persistent = {"env_steps_per_s": global_envs * args.steps / w, "ms_per_step": w / args.steps * 1e3,
                       "ms_per_step_min": wmin / args.steps * 1e3, "ms_per_step_max": wmax / args.steps * 1e3,
@@ -298,7 +369,7 @@ def main():
                                 "no caller in the agent loop)"}
 
     strong = None
-    if world > 1 and args.scaling == "weak":
+    if args.full and world > 1 and args.scaling == "weak":
         strong = {}
         for ge in [int(v) for v in os.environ.get("TRUSS_BENCH_STRONG", "4096,8192").split(",")]:   # (the CPU rehearsal shrinks them)
             b = shard_of(ge)
@@ -311,7 +382,7 @@ def main():
 
     # the state-emitting step (BASELINE configs 3-5 need the observation tensors every step): TRUSS_F_EMIT_OBS
     state = None
-    if rank == 0 and on_gpu:
+    if args.full and rank == 0 and on_gpu:
         ag0, at0 = G[0].contiguous(), T[0].contiguous()
         ob = env.obs_buffers()
         for _ in range(20):
@@ -342,7 +413,7 @@ def main():
 
     if rank == 0:
         per_step_bytes = algorithmic_bytes_per_env_step(topo.N, topo.E) * B
-        kern_s = (dev_ms * 1e-3 if dev_ms is not None else elapsed) / args.steps
+        kern_s = dev_ms_step * 1e-3 if dev_ms_step is not None else step_s
         achieved = per_step_bytes / kern_s / 1e9
         info = topo.solver_info(lib)
         traffic = committed_traffic(ROOT, B, topo.N, topo.E)
@@ -360,15 +431,16 @@ def main():
             state["traffic"] = traffic.get("fused")
         out = {
             "metric": "env steps/sec (batched FEM solves) at 4096 envs",
-            "value": global_envs * args.steps / elapsed,
+            "value": global_envs / step_s,
             "unit": "env-steps/s",
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_min": el_min / args.steps * 1e3,
-            "ms_per_step_max": el_max / args.steps * 1e3,
-            "timed_blocks": BLOCKS,
+            "warmup_steps_run": warm,
+            "ms_per_step": step_s * 1e3,
+            "ms_per_step_min": step_min * 1e3,
+            "ms_per_step_max": step_max * 1e3,
+            "timed_blocks": n_blocks,
             "higher_is_better": True,
             "scaling": args.scaling,
             "vs_baseline": None,
@@ -377,7 +449,7 @@ def main():
             "config": {
                 "workload": "synthetic random-geometry 2-row trusses, 32 nodes / 80 elements / 60 DOF, "
                             "FEM-only env.step (action decode + FP64 assembly/solve + stresses + point), no agent",
-                "path": "step: one launch of truss_step_kernel per env step (truss_step), K launches per timed block",
+                "path": "step: one launch of truss_step_kernel per env step (truss_step), the K timed launches in timed_blocks blocks",
                 "envs_per_gpu": B, "global_envs": global_envs, "nodes": topo.N, "elements": topo.E,
                 "ndof": int(env.ndof), "half_bandwidth": info["half_bandwidth"],
                 "lanes_per_env": info["lanes_per_env"], "rows_per_lane": info["rows_per_lane"],
@@ -394,10 +466,12 @@ def main():
                 # the other two ceilings SURVEY §8d asks for (algorithmic banded flop count, 1e4 per env-step)
                 "fp64_gflops": 1.0e4 * B / kern_s / 1e9, "fp64_frac_of_78.6_TFLOPs": 1.0e4 * B / kern_s / 78.6e12,
             },
-            "persistent_rollout": persistent,
-            "state_emitting_step": state,
             "nonpositive_pivots": st,
+            "full": args.full,
         }
+        if args.full:
+            out["persistent_rollout"] = persistent
+            out["state_emitting_step"] = state
         if strong:
             out["strong"] = strong
         if extras:
@@ -410,7 +484,7 @@ def main():
     # BASELINE configs[2]-[4], after the headline is complete: the line is printed in every case.  A watchdog on every rank ends the
     # process cleanly if the block does not come back (a collective that never completes cannot be interrupted from Python): rank 0
     # then prints the headline with the reason in `configs`.
-    if on_gpu and not args.no_configs:
+    if args.full and on_gpu and not args.no_configs:
         import threading
 
         def give_up():

@@ -1,4 +1,4 @@
-"""Workloads of BASELINE.json configs[2]-[4] as functions (used by bench.py's default `configs` object and by the CLIs under
+"""Workloads of BASELINE.json configs[2]-[4] as functions (used by the `configs` object of bench.py --full and by the CLIs under
 tools/): the batched MADDPG rollout on small_roof, the mixed 32-256-node pool (FEM step and Pareto sweep with one set of
 agents), and large_bridge with its env batch sharded over the ranks present.  One env-step = one agent's modification of
 one design (one `_game_modify`, like the FEM-only metric); a game step of the batched loop

@@ -104,5 +104,5 @@ def run(tm, synthetic, lib, dev, topo, env, G, T, args, B):
         a1.record(); torch.cuda.synchronize()
         extras[tag]["us_per_pool_step_with_obs"] = a0.elapsed_time(a1) * 1e3 / 30
         del p
-    # (BASELINE configs[2]-[4] -- the batched MADDPG rollout, the mixed sweep, large_bridge -- are in bench.py's default `configs` object)
+    # (BASELINE configs[2]-[4] -- the batched MADDPG rollout, the mixed sweep, large_bridge -- are in the `configs` object of bench.py --full)
     return extras

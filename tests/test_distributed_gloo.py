@@ -123,7 +123,7 @@ def _bench_line(extra_args, extra_env=None):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(TRUSS_BENCH_BACKEND="gloo", TRUSS_BENCH_STRONG="12,21", **(extra_env or {}))
-    r = subprocess.run([sys.executable, os.path.join(pc.ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(pc.ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--no-cpu-baseline",
                         "--lib", pc.build_emu()] + extra_args, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -132,7 +132,7 @@ def _bench_line(extra_args, extra_env=None):
 
 
 def test_bench_spawns_its_own_ranks_weak_and_strong():
-    o = _bench_line(["--gpus", "2", "--envs", "8"])
+    o = _bench_line(["--gpus", "2", "--envs", "8", "--full"])
     assert o["n_gpus"] == 2 and o["scaling"] == "weak" and o["timed_blocks"] >= 5
     assert o["config"]["envs_per_gpu"] == 8 and o["config"]["global_envs"] == 16
     assert o["ms_per_step_min"] <= o["ms_per_step"] <= o["ms_per_step_max"]
@@ -142,6 +142,59 @@ def test_bench_spawns_its_own_ranks_weak_and_strong():
     s = _bench_line(["--gpus", "2", "--scaling", "strong", "--global-envs", "11"])
     assert s["scaling"] == "strong" and s["config"]["global_envs"] == 11 and s["config"]["envs_per_gpu"] == 6
     assert abs(s["value"] - 11 / (s["ms_per_step"] * 1e-3)) < 1e-6 * s["value"]
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_them(tmp_path):
+    """a plain one-GPU run (CPU rehearsal): exactly --steps timed steps, no --full legs, and --dump-outputs writes what the
+    last step computed -- the same arrays in two runs, equal to the same W + K steps replayed here"""
+    import bench
+    from truss_mi355 import distributed, synthetic
+    runs = []
+    for d in ("a", "b"):
+        o = _bench_line(["--gpus", "1", "--envs", "8", "--steps", "733", "--dump-outputs", str(tmp_path / d)])
+        assert o["steps"] == 733 and o["timed_blocks"] == 5 and o["warmup_steps_run"] == 1 and not o["full"]
+        assert "persistent_rollout" not in o and "configs" not in o and "cpu_baseline" not in o
+        assert o["ms_per_step_min"] <= o["ms_per_step"] <= o["ms_per_step_max"]
+        assert abs(o["value"] - 8 / (o["ms_per_step"] * 1e-3)) < 1e-6 * o["value"]
+        runs.append({k: np.load(tmp_path / d / f"{k}.npy") for k in bench.DUMP_KEYS})
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{k}.npy" for k in bench.DUMP_KEYS)
+    for k, a in runs[0].items():
+        assert a.dtype == np.float32 and a.shape[0] == 8
+        assert np.array_equal(a, runs[1][k]), k
+    assert bench.timed_blocks(733, 1) == [147, 147, 147, 146, 146]                # the CPU rehearsal: blocks of any size
+    assert bench.timed_blocks(400) == [400] and bench.timed_blocks(25000) == [12500, 12500]     # the GPU: of >= MIN_BLOCK_STEPS
+    assert bench.timed_blocks(50003) == [10001, 10001, 10001, 10000, 10000]
+    env, G, T, _ = distributed.make_rank_env(synthetic.bench_topology(bench.NUM_X, bench.N_EXTRA), 8, 0, lib=pc.emu_lib(),
+                                             seed=1234, n_action_sets=bench.N_ACTION_SETS)
+    env.rollout(G, T, 1)                                                     # --warmup 1, then the timed blocks
+    for k in bench.timed_blocks(733, 1):
+        env.rollout(G, T, k)
+    ref = env.results()
+    for k in bench.DUMP_KEYS:
+        np.testing.assert_array_equal(runs[0][k], ref[k].astype(np.float32), err_msg=k)
+
+
+def test_bench_dump_is_capped():
+    """above the 64 MB cap a fixed sample of env rows is written, with its indices"""
+    import tempfile
+    import bench
+
+    class Env:
+        def results(self):
+            B = 300000
+            return {k: np.full((B, 40), 1.0, np.float32) if k != "sec" else np.tile(np.arange(B, dtype=np.int32)[:, None], (1, 80))
+                    for k in bench.DUMP_KEYS}
+
+    with tempfile.TemporaryDirectory() as d:
+        names = bench.dump_outputs(Env(), d, 1, 2)
+        assert "env_index" in names
+        total = sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+        assert total <= bench.DUMP_CAP_BYTES // 2 + 4096 * len(names) and all(f.endswith(".rank1.npy") for f in os.listdir(d))
+        idx = np.load(os.path.join(d, "env_index.rank1.npy"))
+        sec = np.load(os.path.join(d, "sec.rank1.npy"))
+        assert np.all(np.diff(idx) > 0) and np.array_equal(sec[:, 0], idx.astype(np.float32))
+        bench.dump_outputs(Env(), d, 1, 2)
+        assert np.array_equal(idx, np.load(os.path.join(d, "env_index.rank1.npy")))
 
 
 def test_shard_bounds_cover_the_batch():

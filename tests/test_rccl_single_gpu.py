@@ -123,8 +123,8 @@ def test_bench_distributed_path_on_one_gpu(nccl):
     time and the collective decisions of the `configs` object, as its own process (it owns its process group)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(TRUSS_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    r = subprocess.run([sys.executable, os.path.join(pc.ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu-baseline",
-                        "--configs-budget", "1"], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(pc.ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--full",
+                        "--no-cpu-baseline", "--configs-budget", "1"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

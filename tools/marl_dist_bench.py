@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BASELINE configs[3]: large_bridge (32 nodes / 76 elements), 8192 envs sharded over the GPUs of one node, one MADDPG whose
 gradients are all-reduced over RCCL (bench_configs.large_bridge; the only collective: the env batch shards with no data-path
-exchange).  bench.py's default line carries the same measurement (`configs.large_bridge_8192`).
+exchange).  bench.py --full carries the same measurement (`configs.large_bridge_8192`).
 
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/marl_dist_bench.py [--global-envs 8192]
   python tools/marl_dist_bench.py                      # one GPU: the whole batch on it, no process group"""
