@@ -126,30 +126,59 @@ def gcn_aggregate(lib, adj, h, bias, act, nbr=None):
     return out
 
 
-def split_weights(lib, w):
+def split_weights(lib, w, out=None):
     """w [C <= 224, K] float32 -> int16 [3, 224, KP] (bfloat16 bit patterns, zero padded): the exact three-term split the bf16x3 path
-    of the fused layer kernel reads (`truss_gcn_split_w`; one small launch).  `layer_split_weights` caches it per GCN layer."""
+    of the fused layer kernel reads (`truss_gcn_split_w`; one small launch).  `layer_split_weights` caches it per GCN layer.
+    out: an existing image of that shape to write (in place: capturable, its address stays)."""
     from . import ops
     C, K = w.shape
-    out = torch.empty((3, 224, (K + 15) // 16 * 16), dtype=torch.int16, device=w.device)
+    if out is None:
+        out = torch.empty((3, 224, (K + 15) // 16 * 16), dtype=torch.int16, device=w.device)
+    assert out.shape == (3, 224, (K + 15) // 16 * 16) and out.dtype == torch.int16 and out.is_contiguous()
     ops.call(ops.namespace().gcn_split_w, ops.bind(lib), ops.stream_of(w.device), w, out)
     return out
+
+
+def _refresh_split(lib, layer, hit):
+    """rewrite a cache entry of `layer_split_weights` from the layer's current weights, in place (same buffers)"""
+    w = layer.lin.weight.detach()
+    _, wd, ws = hit
+    if wd.data_ptr() != w.data_ptr():                    # the zero-padded copy (its pad columns stay zero)
+        wd[:, :w.shape[1]].copy_(w)
+    if ws is not None:
+        split_weights(lib, wd, out=ws)
 
 
 def layer_split_weights(lib, layer, k_pad=0):
     """(w, split_weights(w)) of a truss2D_RL.GCNConv, kept on the module and redone when its kernel has changed (training updates the
     weights in place: tensor version counter; load_state_dict / re-materialisation: data pointer).  k_pad > k_in: the kernel's input
-    columns are zero-padded to k_pad first (the 13-feature input layers run at 16 so that they take the 16-byte loaders)."""
+    columns are zero-padded to k_pad first (the 13-feature input layers run at 16 so that they take the 16-byte loaders).
+    A version change rewrites the entry IN PLACE: a captured update (BatchedMARL._train) refreshes the same buffers on every replay
+    (`refresh_actor_caches`) -- a replay changes the weights without bumping their version counters."""
     w = layer.lin.weight
     tag = (w._version, w.data_ptr(), tuple(w.shape), k_pad)
     hit = getattr(layer, "_truss_split", None)
-    if hit is None or hit[0] != tag:
-        wd = w.detach()
-        if k_pad > wd.shape[1]:
-            wd = torch.nn.functional.pad(wd, (0, k_pad - wd.shape[1])).contiguous()
-        hit = (tag, wd, split_weights(lib, wd) if (wd.shape[0] > 32 and wd.shape[1] % 4 == 0) else None)
-        layer._truss_split = hit
+    if hit is not None and hit[0][1:] == tag[1:]:
+        if hit[0][0] != tag[0]:
+            _refresh_split(lib, layer, hit)
+            hit = (tag,) + hit[1:]
+            layer._truss_split = hit
+        return hit[1], hit[2]
+    wd = w.detach()
+    if k_pad > wd.shape[1]:
+        wd = torch.nn.functional.pad(wd, (0, k_pad - wd.shape[1])).contiguous()
+    hit = (tag, wd, split_weights(lib, wd) if (wd.shape[0] > 32 and wd.shape[1] % 4 == 0) else None)
+    layer._truss_split = hit
     return hit[1], hit[2]
+
+
+def refresh_actor_caches(lib, actor):
+    """rewrite every cached weight copy of `actor`'s layers (split images, zero-padded inputs) from its current weights, in
+    place: the tail of the captured MADDPG update, so that inference after a replay sees the weights the replay wrote"""
+    for layer in actor.modules():
+        hit = getattr(layer, "_truss_split", None)
+        if hit is not None:
+            _refresh_split(lib, layer, hit)
 
 
 def gcn_layer(lib, x, adj, w, bias, act, nbr=None, out=None, accumulate=False, precision="bf16x3", w_split=None):
@@ -464,6 +493,12 @@ class BatchedMARL:
                 nets = [n for ag_ in self.rl.agents for n in (ag_.actor_model, ag_.critic_model, ag_.target_actor_model,
                                                                 ag_.target_critic_model)]
                 self.rl._ensure_ready(S, [A[0][0], A[0][1], A[1][0], A[1][1], A[2][0], A[2][1]])
+                # the inference caches of every actor (split images, padded input weights) exist before capture: the captured
+                # update rewrites them in place at its end, so that the rollout acts with the weights each replay wrote
+                with torch.no_grad():
+                    for ag_ in self.rl.agents:
+                        actor_infer(self.lib, ag_.actor_model, [S[0][:1], self.A_n[0], S[2][:1], S[3][:1], S[4][:1], S[6][:1], S[7][:1]],
+                                    nbr=self.nbr, nbr_p=self.nbr_p)
                 snap = [[p.detach().clone() for p in n.parameters()] for n in nets]
                 osnap = [t.clone() for t in self.rl.critics_opt.state_tensors()]    # [] = no step taken yet (one optimiser for the three critics)
                 n_loss = [len(ag_.c_loss) for ag_ in self.rl.agents]
@@ -503,6 +538,9 @@ class BatchedMARL:
                 try:
                     with torch.cuda.graph(g, stream=side):
                         self.rl.train_on_batch(*unpack(bufs))
+                        with torch.no_grad():
+                            for ag_ in self.rl.agents:
+                                refresh_actor_caches(self.lib, ag_.actor_model)
                 finally:
                     restore()       # captured or not: training continues from the pre-warm-up state
                 self._tg = (g, bufs)
@@ -512,6 +550,11 @@ class BatchedMARL:
                 torch.cuda.synchronize(self.device)
                 return self.rl.train_on_batch(S, NS, A, R)
         g, bufs = self._tg
+        # broadcast constants were captured by address: a call that brings another one (or a shape the graph was not captured
+        # for) runs eagerly -- never a copy into an expanded buffer, never the captured adjacency in its place
+        if any(b.dim() and b.stride(0) == 0 and (t.data_ptr() != b.data_ptr() or t.stride() != b.stride() or t.shape != b.shape)
+               for b, t in zip(bufs, flat_in)):
+            return self.rl.train_on_batch(S, NS, A, R)
         pairs = [(b, t) for b, t in zip(bufs, flat_in) if b is not t and b.data_ptr() != t.data_ptr()]
         torch._foreach_copy_([b for b, _ in pairs], [t for _, t in pairs])    # multi-tensor launches for the ~30 input tensors
         g.replay()

@@ -378,8 +378,20 @@ extern "C" int truss_gcn_aggregate(const float *adj, int64_t a_batch_stride, con
   return TRUSS_OK;
 }
 
+// the upper half of a float32 (one truncated bfloat16 term, as a float)
+static inline float emu_bf16_top(float x) {
+  uint32_t u;
+  memcpy(&u, &x, 4);
+  u &= 0xffff0000u;
+  memcpy(&x, &u, 4);
+  return x;
+}
+
 // truss_gcn_layer, CPU stand-in of the MFMA kernel (plain loops, the same operation order: aggregate the input rows, then the
-// product with W^T, then bias / activation / accumulation) -- lets the host-side plumbing of the actors run in the CPU tests
+// product with W^T, then bias / activation / accumulation) -- lets the host-side plumbing of the actors run in the CPU tests.
+// With split weights (w_bf16x3) it does what the bf16x3 kernel does: the weights come from the [3][224][kp] image (not from w),
+// every aggregated input value is split into three truncated bfloat16 terms (tg_split_term), and the six partial products
+// a0 b0 + a0 b1 + a1 b0 + a0 b2 + a1 b1 + a2 b0 are summed in float32; same envelope as the kernel
 extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *) {
   if (!a || a->struct_size != sizeof(truss_gcn_layer_args_t)) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: bad argument block");
   if (!a->x || !a->adj || !a->w || !a->out) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: a required pointer is NULL");
@@ -387,6 +399,19 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *) {
     return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: shape outside the kernel's envelope");
   const int N = a->n_nodes, K = a->k_in, C = a->c_out;
   const long xs = a->x_row_stride ? a->x_row_stride : K, os = a->out_row_stride ? a->out_row_stride : C;
+  const uint16_t *ws = a->w_bf16x3;
+  const int KP = (K + 15) & ~15;
+  if (ws) {
+    const int kn = a->nbr ? a->k_nbr : N;
+    if (C <= 32 || K % 4 != 0 || xs % 4 != 0 || ((size_t)a->x & 15) != 0 || kn > 9 || ((size_t)ws & 15) != 0)
+      return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: the bf16x3 path takes c_out 33..224, k_in % 4 == 0, 16-byte aligned x / split weights, <= 9 terms per row");
+  }
+  auto wterm = [&](int t, int c, int k) {
+    uint32_t u = (uint32_t)ws[((size_t)t * 224 + c) * KP + k] << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+  };
   std::vector<float> xa((size_t)N * K);
   for (int b = 0; b < a->n_batch; ++b) {
     const float *A = a->adj + (size_t)b * a->a_batch_stride;
@@ -407,7 +432,21 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *) {
     for (int i = 0; i < N; ++i)
       for (int c = 0; c < C; ++c) {
         float acc = 0.0f;
-        for (int k = 0; k < K; ++k) acc += xa[(size_t)i * K + k] * a->w[(size_t)c * K + k];
+        if (ws) {
+          for (int k = 0; k < K; ++k) {
+            const float x0 = emu_bf16_top(xa[(size_t)i * K + k]), r1 = xa[(size_t)i * K + k] - x0;
+            const float x1 = emu_bf16_top(r1), x2 = emu_bf16_top(r1 - x1);
+            const float w0 = wterm(0, c, k), w1 = wterm(1, c, k), w2 = wterm(2, c, k);
+            acc += x2 * w0;            // small partial products first (each product of two bfloat16 terms is exact in float32)
+            acc += x1 * w1;
+            acc += x0 * w2;
+            acc += x1 * w0;
+            acc += x0 * w1;
+            acc += x0 * w0;
+          }
+        } else {
+          for (int k = 0; k < K; ++k) acc += xa[(size_t)i * K + k] * a->w[(size_t)c * K + k];
+        }
         acc += a->bias ? a->bias[c] : 0.0f;
         if (a->act == 1) acc = acc > 0.0f ? acc : 0.0f;
         else if (a->act == 2) acc = 1.0f / (1.0f + expf(-acc));
@@ -448,7 +487,7 @@ extern "C" int truss_gcn_level(const truss_gcn_layer_args_t *layers, int32_t n_l
   return TRUSS_OK;
 }
 
-// the exact three-term bfloat16 split of the bf16x3 path (host restatement); the emulated layer itself sums in float32
+// the exact three-term bfloat16 split of the bf16x3 path (host restatement), the image the emulated bf16x3 layer reads
 extern "C" int truss_gcn_split_w(const float *w, int32_t c_out, int32_t k_in, uint16_t *out, void *) {
   if (!w || !out || c_out < 1 || k_in < 1 || c_out > 224) return tb_fail(TRUSS_EINVAL, "truss_gcn_split_w: bad argument");
   const int KP = (k_in + 15) & ~15, CP = 224;
