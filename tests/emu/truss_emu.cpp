@@ -19,8 +19,26 @@ struct float4 {
 #define TRUSS_UNROLL
 #define TB_STREAM_STORE(p, v) (*(p) = (v))
 #define TB_OBS_STORE(p, v) (*(p) = (v))
+#ifdef TRUSS_EMU_MUTANTS
+// Test-only build (tests/test_solver_geometry.py): truss_emu_set_mutant(m) swaps one float64 shim for a float32 one, to prove
+// that the solver criteria of tests/fem_reference.py catch it.  1: pivot reciprocal rounded to float32 (no Newton refinement),
+// 2: 1/L of the elements in float32, 3: reactions accumulated in float32.  0: the plain emulator.
+static int g_emu_mutant = 0;
+extern "C" int truss_emu_set_mutant(int m) {
+  g_emu_mutant = m;
+  return 0;
+}
+static inline void tb_lds_add(double *p, double v) {
+  if (g_emu_mutant == 3) *p = (double)((float)*p + (float)v);
+  else *p += v;
+}
+static inline double tb_rcp(double d) { return g_emu_mutant == 1 ? (double)(float)(1.0 / d) : 1.0 / d; }
+#define TB_EMU_RSQRT(x) (g_emu_mutant == 2 ? (double)(1.0f / sqrtf((float)(x))) : 1.0 / sqrt(x))
+#else
 static inline void tb_lds_add(double *p, double v) { *p += v; }
 static inline double tb_rcp(double d) { return 1.0 / d; }
+#define TB_EMU_RSQRT(x) (1.0 / sqrt(x))
+#endif
 // The emulator's lanes know their wave (cross-lane stand-ins below); the product's lane struct does not.
 template <class LN>
 struct EmuLane : LN {
@@ -31,7 +49,7 @@ static inline EmuLane<LN> *emu_peers(LN &ln) { return static_cast<EmuLane<LN> &>
 // DPP row broadcast stand-in: the value lane `src` of this lane's team computed in the previous phase
 template <class LN>
 static inline double tb_team_bcast(LN &ln, int src) { return emu_peers(ln)[ln.lane - ln.gs + src].bx; }
-static inline double tb_rsqrt(double x) { return 1.0 / sqrt(x); }
+static inline double tb_rsqrt(double x) { return TB_EMU_RSQRT(x); }
 static inline float tb_rcpf(float d) { return 1.0f / d; }
 // min / max over the lanes of an env: the partials the lanes left in the previous phase
 template <class LN>

@@ -13,19 +13,23 @@ from conftest import GOLDEN, ROOT, SCENARIOS
 
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU_LIB = os.path.join(EMU_DIR, "libtruss_emu.so")
+EMU_MUTANT_LIB = os.path.join(EMU_DIR, "libtruss_emu_mutant.so")
 
 
-def build_emu():
+def build_emu(mutants=False):
+    """the lane emulator, rebuilt when a source is newer; mutants=True: the test-only build with
+    truss_emu_set_mutant() (tests/test_solver_geometry.py), a separate library"""
     src = os.path.join(EMU_DIR, "truss_emu.cpp")
+    out = EMU_MUTANT_LIB if mutants else EMU_LIB
     deps = [src, os.path.join(ROOT, "mop-truss-marl_amd", "csrc", "truss_body.h"),
             os.path.join(ROOT, "mop-truss-marl_amd", "csrc", "truss_host.h"),
             os.path.join(ROOT, "include", "truss_mi355.h")]
-    if (not os.path.exists(EMU_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(EMU_LIB) for d in deps):
+    if (not os.path.exists(out)) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         # TRUSS_EMU_CXXFLAGS: e.g. -DTRUSS_PIPELINE=1 to emulate the alternative factorisation schedule
-        extra = os.environ.get("TRUSS_EMU_CXXFLAGS", "").split()
+        extra = os.environ.get("TRUSS_EMU_CXXFLAGS", "").split() + (["-DTRUSS_EMU_MUTANTS"] if mutants else [])
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-Wno-unknown-pragmas"] + extra + ["-o", EMU_LIB, src], cwd=EMU_DIR)
-    return EMU_LIB
+                               "-Wno-unknown-pragmas"] + extra + ["-o", out, src], cwd=EMU_DIR)
+    return out
 
 
 def emu_lib():

@@ -175,7 +175,8 @@ def test_full_size_properties(lib):
     """BASELINE size (32 nodes / 80 elements / 4096 envs): size-independent properties.
     (1) a random 256-env sample agrees with the oracle; (2) equilibrium: reactions balance the applied
     load; (3) work-energy: U = 1/2 d.P; (4) determinism: two runs are bit-identical;
-    (5) linearity: doubling the load doubles displacements and member forces."""
+    (5) linearity: doubling the load doubles displacements and member forces; (6) with horizontal loads in half the envs the
+    reactions balance both load components and U = 1/2 d.P still holds."""
     topo = synthetic.bench_topology(16, 4)
     B = 4096
     batch = synthetic.random_batch(topo, B, 77)
@@ -227,6 +228,22 @@ def test_full_size_properties(lib):
     ra, rb = ea.results(), eb.results()
     np.testing.assert_allclose(rb["disp_f64"], 2.0 * ra["disp_f64"], rtol=1e-9, atol=1e-18)
     np.testing.assert_allclose(rb["q0_f64"], 2.0 * ra["q0_f64"], rtol=1e-8, atol=1e-6)
+    # (6) horizontal loads in half the envs: the reactions balance both components, work = energy with both
+    rng = np.random.default_rng(79)
+    b3 = dict(b1)
+    b3["load_x"] = np.where(rng.random(B) < 0.5, rng.uniform(-0.6, 0.6, B) * np.abs(batch["load_y"]), 0.0)
+    ec = pc.make_env(lib, topo, b3)
+    ec.analyze()
+    rc = ec.results()
+    assert int(rc["status"].sum()) == 0
+    np.testing.assert_allclose(rc["reactions"][:, 1] + rc["reactions"][:, 3], -total, rtol=1e-8)
+    rxc = rc["reactions"][:, 0] + rc["reactions"][:, 2]
+    assert np.abs(rxc + b3["load_x"] * nloaded).max() < 1e-8 * np.abs(total).max()
+    Px = np.zeros((B, topo.N))
+    for b in range(B):
+        Px[b, topo.load_mask[1 if batch["is_roof"][b] else 0].astype(bool)] = b3["load_x"][b]
+    work = 0.5 * ((Px * rc["disp_f64"][:, :, 0]).sum(axis=1) + (P * rc["disp_f64"][:, :, 1]).sum(axis=1))
+    np.testing.assert_allclose(rc["energy"], work, rtol=1e-9)
 
 
 @pytest.mark.parametrize("case", ["bench_1000", "bench_8200", "bench_8_lanes", "large_symmetric", "small_bridge", "train_12n", "nodes_128"])
