@@ -222,7 +222,8 @@ int truss_obs(const truss_topo_t *t, const truss_obs_args_t *args, void *stream)
  * utils.union_rectangles_fastest (:275-342), which the reward block of master_DDPG_truss2D_MO.run()
  * (:263-368) calls 5 + 6 times per archived solution, for B envs at once.
  *
- * Per env: n_points[b] rows [obj1, obj2, con1, con2] (n <= max_points <= 64).
+ * Per env: n_points[b] rows [obj1, obj2, con1, con2] (n <= max_points <= 256: one wave per env up to 64 rows,
+ *           one 256-thread workgroup per env above; the same rules and the same results either way).
  *   feasible  = not (con1 > 1 or con2 > 1)                                   (utils.py:18-22)
  *   front     = feasible rows no other feasible row beats in BOTH objectives (strict), identical rows once,
  *               sorted by obj1 (ties: obj2, then input order -- the reference's tie order is a set order)
@@ -237,7 +238,7 @@ int truss_obs(const truss_topo_t *t, const truss_obs_args_t *args, void *stream)
  * All pointers are device memory; outputs may be NULL to skip them.
  */
 #define TRUSS_FRONT_TRUNCATE 0x1u
-#define TRUSS_FRONT_MAXP 64
+#define TRUSS_FRONT_MAXP 256
 
 typedef struct truss_front_args {
   size_t struct_size;

@@ -10,7 +10,7 @@ static int tb_fail(int code, const std::string &msg);
 static inline int tb_front_check(const truss_front_args_t *a) {
   if (!a || a->struct_size != sizeof(truss_front_args_t)) return tb_fail(TRUSS_EINVAL, "truss_front: bad args / struct_size");
   if (a->n_envs < 0 || a->max_points < 1 || a->max_points > TRUSS_FRONT_MAXP)
-    return tb_fail(TRUSS_EINVAL, "truss_front: max_points must be 1..64");
+    return tb_fail(TRUSS_EINVAL, "truss_front: max_points must be 1..256");
   if (!a->points || !a->n_points) return tb_fail(TRUSS_EINVAL, "truss_front: points / n_points NULL");
   if ((a->flags & TRUSS_FRONT_TRUNCATE) && a->max_front < 2) return tb_fail(TRUSS_EINVAL, "truss_front: max_front < 2");
   return TRUSS_OK;

@@ -56,7 +56,7 @@ class FrontArgs(C.Structure):
 
 
 F_FRONT_TRUNCATE = 0x1
-FRONT_MAXP = 64
+FRONT_MAXP = 256
 
 
 class TrussError(RuntimeError):

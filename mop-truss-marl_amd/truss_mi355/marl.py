@@ -27,7 +27,18 @@ Differences from the per-env loop, all forced by batching and documented here:
   D4  when an agent's move is infeasible its next state in the replay is the first feasible agent's
       (the reference draws a random survivor, :380-407); the Pareto-graph inputs (x_p, A_p) of the next
       states are those of the step-start front;
-  D5  exploration noise is drawn on the device (same law as truss2D_RL.OUNoise: theta (mu - a) dt + sigma N(0,1)).
+  D5  exploration noise is drawn on the device (same law as truss2D_RL.OUNoise: theta (mu - a) dt + sigma N(0,1));
+  D6  (design game) the symmetry coin of each move is the top bit of a splitmix64 hash of (engine seed, global env id, game
+      step, member index in the step-start archive, agent) -- `design_coins` -- instead of the reference's random.random()
+      >= 0.5 per _game_modify call (test/*/truss2D_ENV.py:459-553): the same Bernoulli(0.5) law, reproducible by a host
+      model and independent of `pair_capacity` and of the chunk order.
+
+The design game (`game="test"`, the reference's test copies test/0?_*/code): trained agents modify mirror-symmetric
+designs with a coin per move, the archive keeps up to MAX_FRONT = 50 members, nothing is trained (train_period = 0) and
+the last step culls the archive plus all of that step's candidates WITHOUT truncation (simple_cull_final, master…:424-428).
+Every chunk's candidates are collected into step-wide buffers (slot = 3 member + agent) and the step ends with ONE cull over
+the P archive rows + 3 P candidates (the wide front kernel takes up to 256 rows): D1 does not apply to this game.
+`design_episode` plays a whole episode.
 """
 from __future__ import annotations
 
@@ -37,6 +48,7 @@ import time
 import numpy as np
 import torch
 
+from . import _lib
 from . import reward as RW
 from .batched import BatchedTruss
 from .topology import TrussTopology
@@ -343,16 +355,57 @@ class DeviceReplay:
         return pick(self.S), [pick(ns) for ns in self.NS], self.a_geo[i], self.a_topo[i], self.R[i]
 
 
+_SM64 = (0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB)
+
+
+def _splitmix64(z):
+    """splitmix64 finaliser on int64 tensors (two's complement wrap-around == uint64 arithmetic; logical shifts by mask)"""
+    s64 = lambda c: c - (1 << 64) if c >= 1 << 63 else c
+    srl = lambda v, k: (v >> k) & ((1 << (64 - k)) - 1)
+    z = z + s64(_SM64[0])
+    z = (z ^ srl(z, 30)) * s64(_SM64[1])
+    z = (z ^ srl(z, 27)) * s64(_SM64[2])
+    return z ^ srl(z, 31)
+
+
+def design_coins(seed, env_ids, game_step, members):
+    """D6: the symmetry coin of every move of the design game, uint8 [K, 3] (agent a in column a) for the pairs (env_ids[k],
+    members[k]) of game step `game_step`: the top bit of splitmix64(splitmix64(seed) ^ (env << 26 | step << 10 | member << 2 | agent))
+    (env < 2^38, step < 2^16, member < 256).  A pure function of those fields: the same on any device, for any pair order."""
+    dev = env_ids.device
+    key = (env_ids.to(torch.int64)[:, None] << 26) | (int(game_step) << 10) | (members.to(torch.int64)[:, None] << 2) \
+        | torch.arange(3, dtype=torch.int64, device=dev)[None, :]
+    h0 = _splitmix64(torch.tensor(int(seed), dtype=torch.int64, device=dev))
+    return (_splitmix64(key ^ h0) < 0).to(torch.uint8)
+
+
 class BatchedMARL:
-    def __init__(self, topo: TrussTopology, n_envs: int, maddpg, *, max_front: int = 20, lib=None, device=None,
+    """game: "train" (the train copy: MAX_FRONT 20, no coin, culls of at most 64 rows, D1) or "test" (the design game of the
+    test copies, see the module docstring: needs a topology built with `symmetry=`; MAX_FRONT 50 unless max_front says
+    otherwise).  env_ids: global ids of the B envs (the coin's env field; default 0..B-1)."""
+
+    def __init__(self, topo: TrussTopology, n_envs: int, maddpg, *, max_front: int | None = None, lib=None, device=None,
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
-                 pair_capacity: int | None = None, tune_update_gemms: bool = True):
+                 pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None):
+        if game not in ("train", "test"):
+            raise ValueError(f"game must be 'train' or 'test', got {game!r}")
+        if game == "test" and len(topo.sym_nodes) == 0:
+            raise ValueError("game='test' modifies mirror-symmetric designs: build the topology with symmetry='small' or 'large'")
+        if max_front is None:
+            max_front = 50 if game == "test" else 20
+        self.game = game
         self.topo, self.B, self.P = topo, int(n_envs), int(max_front)
         self.rl = maddpg
         if tune_update_gemms and (device is None or torch.device(device).type == "cuda"):
             enable_gemm_tuning()      # library GEMM per (fixed) shape of the update, chosen during its warm-up (23 -> 14 ms per update)
-        # members whose candidates fit one cull: P archive rows + 3 candidates per member <= the front kernel's 64 rows
-        self.Gm = max(1, min(self.P, (64 - self.P) // 3))
+        if game == "test":
+            # one cull per game step over the P archive rows + the 3 candidates of every member
+            if 4 * self.P > _lib.FRONT_MAXP:
+                raise ValueError(f"game='test': max_front {self.P} needs {4 * self.P} rows per cull, the front kernel takes {_lib.FRONT_MAXP}")
+            self.Gm = self.P
+        else:
+            # members whose candidates fit one cull: P archive rows + 3 candidates per member <= the front kernel's 64 rows
+            self.Gm = max(1, min(self.P, (64 - self.P) // 3))
         # (env, member) pairs per pass: the env objects below hold that many designs (3 x as many candidates)
         self.cap = int(pair_capacity) if pair_capacity else min(self.B * self.Gm, 4 * self.B)
         self.cap = max(self.cap, self.B)
@@ -377,6 +430,12 @@ class BatchedMARL:
         self.batch_size, self.hv_margin = batch_size, hv_margin
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seed)
+        self.seed = int(seed)
+        self.env_ids = (torch.arange(B, dtype=torch.int64, device=dev) if env_ids is None else
+                        torch.as_tensor(np.asarray(env_ids, np.int64), device=dev))
+        assert self.env_ids.shape == (B,)
+        self.end_step = None           # design game: the game step whose cull is the final one (design_episode sets it)
+        self.final = None              # design game: the final front after that step (see _design_cull)
         self.game_step = 1
         self._steps_dev = torch.zeros((), dtype=torch.int64, device=self.device)
         self._synced = False
@@ -421,6 +480,7 @@ class BatchedMARL:
         self.n.fill_(1)
         self.ref_points.fill_(1.0)
         self.game_step = 1
+        self.final = None
 
     # ---- observation tensors in the networks' order ----
     def _obs(self, env, pts0, n0, index, rep=1, k=None, o=None, graph=None):
@@ -560,9 +620,17 @@ class BatchedMARL:
         g.replay()
 
     # ---- one game step of every env (run() :198-705) ----
-    def game_step_all(self, train: bool = True, explore: bool = True, train_iters: int = 1, update: bool = True):
-        """train: push accepted transitions to the replay and (with `update`) run `train_iters` MADDPG updates from it;
-        update=False leaves the updates to the caller (MixedMARL: one set of agents over several size classes)."""
+    def game_step_all(self, train: bool | None = None, explore: bool = True, train_iters: int = 1, update: bool = True):
+        """train: push accepted transitions to the replay and (with `update`) run `train_iters` MADDPG updates from it
+        (default: True in the train game; the design game does not train); update=False leaves the updates to the caller
+        (MixedMARL: one set of agents over several size classes).
+        Design game: every move gets its coin (D6), the step ends with one cull of the archive and all candidates, truncated to
+        max_front -- or, at game step `end_step`, not truncated: the final front (`self.final`).  The result adds G_U [B]."""
+        test = self.game == "test"
+        if train is None:
+            train = not test
+        if test and train:
+            raise ValueError("the design game (game='test') does not train (train_period = 0)")
         B, P, Gm = self.B, self.P, self.Gm
         pts0, n0 = self.pts.clone(), self.n.clone()                   # front_no / Pf_HV of this step (:203-209)
         y0, sec0 = self.arch_y.clone(), self.arch_sec.clone()
@@ -573,6 +641,11 @@ class BatchedMARL:
         N, E = self.topo.N, self.topo.E
         arP = self._const("arP", lambda: torch.arange(P, device=dev))
         n_max = int(n0.max().item())
+        if test:                      # step-wide candidate buffers, slot = 3 member + agent (empty slot = infeasible row [0, 0, 2, 0])
+            gsum = torch.zeros((B,), dtype=torch.float64, device=dev)
+            stepP = self._const("stepP", lambda: torch.tensor([0.0, 0.0, 2.0, 0.0], dtype=torch.float64, device=dev).expand(B, 3 * P, 4)).clone()
+            stepY = torch.zeros((B, 3 * P, N), dtype=torch.float32, device=dev)
+            stepS = torch.zeros((B, 3 * P, E), dtype=torch.int32, device=dev)
         for g0 in range(0, n_max, Gm):                                # member groups whose candidates fit one cull
             # live (env, member) pairs of this group, member-major: pair k = (env pb[k], member pm[k])
             livemask = (arP[None, g0:g0 + Gm] < n0[:, None])          # [B, Gm]
@@ -598,18 +671,30 @@ class BatchedMARL:
                 eC.x[:3 * K], eC.target[:3 * K], eC.env_params[:3 * K] = cx.repeat(3, 1), ct.repeat(3, 1), cp.repeat(3, 1)
                 eC.y[:3 * K], eC.sec[:3 * K] = py.repeat(3, 1), ps.repeat(3, 1)
                 a_geo, a_topo = torch.cat(geo, 0).contiguous(), torch.cat(topo, 0).contiguous()
-                oC = eC.step(a_geo, a_topo, clamp_inplace=True, n_active=3 * K, obs=True)   # clamped actions go to the replay (:375);
+                coin = None
+                if test:                                                                     # D6: agent-major like the candidates
+                    coin = design_coins(self.seed, self.env_ids[idx], self.game_step, ms).t().contiguous().view(-1)
+                oC = eC.step(a_geo, a_topo, coin, clamp_inplace=True, n_active=3 * K, obs=not test)   # clamped actions go to the replay (:375);
                 self._steps_dev += 3 * K                                                     # step + next-state observations: one launch
-                NSall = self._obs(eC, p0, nn0, ms, rep=3, k=3 * K, o=oC, graph=(S["x_p"], S["A_p"]))
+                NSall = None if test else self._obs(eC, p0, nn0, ms, rep=3, k=3 * K, o=oC, graph=(S["x_p"], S["A_p"]))
                 tk = self._tick("candidate step + obs", tk)
                 points = eC.point[:3 * K].view(3, K, 4).permute(1, 0, 2).double().contiguous()
                 cand_y = eC.y[:3 * K].view(3, K, -1).permute(1, 0, 2)
                 cand_sec = eC.sec[:3 * K].view(3, K, -1).permute(1, 0, 2)
-                R, _, _, _ = RW.difference_reward(p0, nn0, p0, nn0, p0[ark, ms, :2].contiguous(), points, self.ref_points[idx].contiguous(),
-                                                  nn0, max_front=P, lib=self.lib)
+                R, G_U, _, _ = RW.difference_reward(p0, nn0, p0, nn0, p0[ark, ms, :2].contiguous(), points, self.ref_points[idx].contiguous(),
+                                                    nn0, max_front=P, lib=self.lib)
                 rsum.index_add_(0, idx, R)
                 tk = self._tick("reward", tk)
                 ok = (points[:, :, 2:4] <= 1).all(dim=2)                                      # archive candidates (:372)
+                if test:                                                                      # collected; culled once after the last chunk
+                    gsum.index_add_(0, idx, G_U)
+                    slot = (ms * 3)[:, None] + self._const("ar3", lambda: torch.arange(3, device=dev)[None, :])
+                    stepP[idx[:, None], slot] = torch.cat([points[:, :, :2], torch.where(ok, points[:, :, 2], 2.0)[:, :, None],
+                                                           points[:, :, 3:]], dim=2)
+                    stepY[idx[:, None], slot] = cand_y
+                    stepS[idx[:, None], slot] = cand_sec
+                    tk = self._tick("archive update", tk)
+                    continue
                 # ---- archive update (D1): front of (working archive + the feasible candidates of this chunk's members) ----
                 C3 = 3 * Gm
                 slot = ((ms - g0) * 3)[:, None] + self._const("ar3", lambda: torch.arange(3, device=dev)[None, :])   # [K, 3] candidate slot of (pair, agent)
@@ -657,14 +742,78 @@ class BatchedMARL:
                     added += self.replay.add(accepted.any(dim=1), S, NSv, ag, at, R.float(), src=src)
                 tk = self._tick("replay", tk)
         # ---- end of the game step (:430-473, 642) ----
-        hv = RW.front_hv(self.pts.contiguous(), self.n, None, 0, self.lib)
+        if test:
+            final = self.end_step is not None and self.game_step >= self.end_step
+            fin = self._design_cull(stepP, stepY, stepS, final)
+            tk = self._tick("archive update", tk)
+        if test and final:
+            hv = dict(hv_front=fin["hv"], metrics=fin["metrics"])
+            n_out = fin["n"].clone()
+        else:
+            hv = RW.front_hv(self.pts.contiguous(), self.n, None, 0, self.lib)
+            n_out = self.n.clone()
         self.ref_points = torch.clamp(self.ref_points + self.hv_margin, max=1.0)
         self.game_step += 1
         if update:
             self.train_from_replay(train_iters if train else 0)
         tk = self._tick("train", tk)
-        return dict(hv=hv["hv_front"], n_front=self.n.clone(), sum_distance=hv["metrics"][:, 3], reward=rsum, replay_added=added,
-                    replay_size=self.replay.size)
+        out = dict(hv=hv["hv_front"], n_front=n_out, sum_distance=hv["metrics"][:, 3], reward=rsum, replay_added=added,
+                   replay_size=self.replay.size)
+        if test:
+            out["G_U"] = gsum
+        return out
+
+    def _design_cull(self, candP, candY, candS, final):
+        """Design game: the ONE cull of a game step, over the archive (P rows, dead rows marked infeasible) + the step's 3 P
+        candidate slots.  Truncated to max_front (D3) and written to the archive; at the final step not truncated (simple_cull_final,
+        master…:424-428, 680): the archive is left as it was and `self.final` = dict(points [B, 4P, 4] (objectives clipped to <= 1
+        like the archive's, :683-686), y [B, 4P, N], sec [B, 4P, E], n [B], hv [B], metrics [B, 5]), rows beyond n zero."""
+        B, P, dev = self.B, self.P, self.device
+        arP = self._const("arP", lambda: torch.arange(P, device=dev))
+        origp = torch.cat([self.pts, candP], dim=1)
+        allp = origp.clone()
+        allp[:, :P, 2] = torch.where(arP[None, :] >= self.n[:, None], 2.0, allp[:, :P, 2])   # infeasible marker
+        fr = RW.front_hv(allp, self._const("step_rows", lambda: torch.full((B,), 4 * P, dtype=torch.int32, device=dev)), None,
+                         max_front=0 if final else P, lib=self.lib)
+        rows = self._const("rows", lambda: torch.arange(B, device=dev)[:, None])
+        fidx = fr["front_idx"] if final else fr["front_idx"][:, :P]
+        fidx = fidx.long()
+        take, live = fidx.clamp(min=0), (fidx >= 0)[:, :, None]
+        newp = torch.where(live, origp[rows, take], 0.0)
+        newp[:, :, 0:2].clamp_(max=1.0)                                                     # :434-436
+        newy = torch.where(live, torch.cat([self.arch_y, candY], dim=1)[rows, take], 0.0)
+        news = torch.where(live, torch.cat([self.arch_sec, candS], dim=1)[rows, take], 0)
+        if final:
+            self.final = dict(points=newp, y=newy, sec=news, n=fr["n_front"], hv=fr["hv_front"], metrics=fr["metrics"])
+        else:
+            self.pts, self.arch_y, self.arch_sec, self.n = newp, newy, news, fr["n_front"]
+        return self.final if final else None
+
+    def design_episode(self, end_step: int = 500, explore: bool = True):
+        """One episode of the design game (game="test") from the state `reset` left: game steps game_step .. end_step, the last
+        one ending in the untruncated final cull.  Returns device tensors: hv [T, B] and n_front [T, B] per step (hyperS and
+        numHV of master…:662-664; the last row is the final front's), R [B, 3] and G_U [B] summed over the episode (R0..R2, Gr of
+        cal_success.py), and final = dict(points, y, sec, n, hv, metrics) (see _design_cull)."""
+        if self.game != "test":
+            raise ValueError("design_episode plays the design game: build the engine with game='test'")
+        T = int(end_step) - self.game_step + 1
+        if T < 1:
+            raise ValueError(f"end_step {end_step} is before the current game step {self.game_step}")
+        B, dev = self.B, self.device
+        hv = torch.empty((T, B), dtype=torch.float64, device=dev)
+        nf = torch.empty((T, B), dtype=torch.int32, device=dev)
+        R = torch.zeros((B, 3), dtype=torch.float64, device=dev)
+        G_U = torch.zeros((B,), dtype=torch.float64, device=dev)
+        self.end_step = int(end_step)
+        try:
+            for t in range(T):
+                o = self.game_step_all(train=False, explore=explore)
+                hv[t], nf[t] = o["hv"], o["n_front"]
+                R += o["reward"]
+                G_U += o["G_U"]
+        finally:
+            self.end_step = None
+        return dict(hv=hv, n_front=nf, R=R, G_U=G_U, final=self.final)
 
     def _const(self, name, make):
         """small constant device tensors of the game step (index ranges, fill patterns), made once"""
@@ -712,6 +861,8 @@ class MixedMARL:
     replays in turn (a batch is of one class: its tensors have that class's shapes)."""
 
     def __init__(self, classes, maddpg, *, bucket_envs=64, rank=0, world=1, **engine_kw):
+        """engine_kw go to every class's BatchedMARL (game="test": every class brings its own symmetric topology; the coin's env
+        field is the env's global id, `global_ids`, where class c's envs are numbered after those of classes 0..c-1)"""
         from .pool import deal_buckets
         self.classes = [(t, int(n)) for t, n in classes]
         self.share = deal_buckets([n for _, n in self.classes], bucket_envs, world)
@@ -721,7 +872,10 @@ class MixedMARL:
             if n_local:
                 self.class_ids.append(c)
                 self.ranges.append(self.share[rank][c])
-                self.engines.append(BatchedMARL(topo, n_local, maddpg, **engine_kw))
+                kw = dict(engine_kw)
+                if kw.get("game", "train") == "test":
+                    kw["env_ids"] = sum(n for _, n in self.classes[:c]) + self.global_ids(len(self.engines))
+                self.engines.append(BatchedMARL(topo, n_local, maddpg, **kw))
         self.rl = maddpg
         self._turn = 0
 
@@ -737,7 +891,16 @@ class MixedMARL:
         for e, b in zip(self.engines, per_class):
             e.reset(b["x"], b["target"], b["y_max"], b["d_min"], b["max_def"], b["load_x"], b["load_y"], b["is_roof"], b["y"], b["sec"])
 
-    def game_step_all(self, train: bool = True, explore: bool = True, train_iters: int = 1):
+    def design_episode(self, end_step: int = 500, explore: bool = True):
+        """BatchedMARL.design_episode of every class (game="test"): per_class = their results; hv / n_front [T, B_local] and
+        R / G_U concatenated over the classes in engine order"""
+        outs = [e.design_episode(end_step=end_step, explore=explore) for e in self.engines]
+        cat = lambda k, d: torch.cat([o[k] for o in outs], dim=d)
+        return dict(per_class=outs, hv=cat("hv", 1), n_front=cat("n_front", 1), R=cat("R", 0), G_U=cat("G_U", 0))
+
+    def game_step_all(self, train: bool | None = None, explore: bool = True, train_iters: int = 1):
+        if train is None:
+            train = self.engines[0].game != "test"
         outs = [e.game_step_all(train=train, explore=explore, update=False) for e in self.engines]
         done = 0
         if train:
