@@ -325,6 +325,31 @@ int truss_gcn_layer(const truss_gcn_layer_args_t *args, void *stream);
  *          [n_batch * n_nodes][k_in] contiguous -- what the backward pass of the layer needs (dW = dZ^T X'). */
 int truss_gcn_level(const truss_gcn_layer_args_t *layers, int32_t n_layers, float *const *x_agg, void *stream);
 
+/* The BACKWARD of such a level in one launch: for every layer i of layers[] (shapes, adj, a_batch_stride, w and act as the forward
+ * took them; x, bias and out of layers[i] are not read), from the gradient of the layer's output,
+ *   dZ = d_out * act'(out)   (relu: out > 0, sigmoid: out (1 - out), none: 1; never stored)
+ *   d_b = sum over rows of dZ,   d_w = dZ^T X',   d_x = A^T (dZ W)
+ * float32 with float32 accumulation on MFMA (v_mfma_f32_32x32x2_f32).  replaces: the backward half of the MADDPG update
+ * (truss2D_RL.py:561-689) as TensorFlow's autodiff runs it through the GCN layers of the actors / critics -- per layer a
+ * ReluGrad / SigmoidGrad, three MatMuls, a BiasAddGrad -- which is bound by its kernel count at batch 32.  Every output element has
+ * one owner and every sum a fixed order (no atomics): results are bitwise reproducible from call to call.  More than 24 layers are
+ * run as consecutive launches, as in the forward.
+ *   d_out  [n_batch * n_nodes][c_out] contiguous       out    the same: the layer's forward output
+ *   x_agg  [n_batch * n_nodes][k_in]: X' = A X as truss_gcn_level stored it; required iff d_w is asked for
+ *   d_w [c_out][k_in], d_b [c_out], d_x [n_batch * n_nodes][k_in]: each written in full where given, NULL = not wanted (a layer
+ *   with all three NULL costs nothing).  d_x must not alias d_out / out (TRUSS_EINVAL), nor may outputs overlap each other.
+ * Envelope: dense adjacency (nbr == NULL; a sparsity pattern is refused), n_nodes <= 64, c_out <= 224, k_in <= 256, float32
+ * (w_bf16x3 == NULL, accumulate == 0), any n_batch; anything else TRUSS_EUNSUPPORTED with nothing written.  Device pointers. */
+typedef struct truss_gcn_level_bwd {
+  const float *d_out;
+  const float *out;
+  const float *x_agg;
+  float *d_w;
+  float *d_b;
+  float *d_x;
+} truss_gcn_level_bwd_t;
+int truss_gcn_level_backward(const truss_gcn_layer_args_t *layers, int32_t n_layers, const truss_gcn_level_bwd_t *bwd, void *stream);
+
 /* w [c_out <= 224][k_in] float32 -> w_bf16x3 [3][224][kp] bfloat16 bit patterns (kp = (k_in + 15) & ~15; rows >= c_out and columns >=
  * k_in are written as zeros: the layer kernel reads whole 224 x 16 slabs by LDS-DMA): the exact
  * three-term split the bf16x3 path of truss_gcn_layer reads.  Once per weight version; device pointers, 16-byte aligned output. */

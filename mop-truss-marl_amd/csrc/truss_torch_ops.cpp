@@ -1,6 +1,7 @@
 // truss_torch_ops.cpp -- PyTorch custom operators in front of the C ABI of include/truss_mi355.h.
 //
-//   torch.ops.truss_mi355.step / rollout / obs / front / gcn_aggregate / gcn_aggregate_sparse / gcn_layer / gcn_level
+//   torch.ops.truss_mi355.step / rollout / obs / front / gcn_aggregate / gcn_aggregate_sparse / gcn_layer / gcn_level /
+//   gcn_level_backward
 //
 // The reference's hot path runs inside TensorFlow ops on its side of the loop (truss2D_RL.py:328-354); here the env
 // step itself is an operator of the host framework: tensors in, tensors mutated in place, launched on the stream the
@@ -31,6 +32,7 @@ struct Backend {
   int (*gcn_layer)(const truss_gcn_layer_args_t *, void *) = nullptr;
   int (*gcn_split)(const float *, int32_t, int32_t, uint16_t *, void *) = nullptr;
   int (*gcn_level)(const truss_gcn_layer_args_t *, int32_t, float *const *, void *) = nullptr;
+  int (*gcn_level_bwd)(const truss_gcn_layer_args_t *, int32_t, const truss_gcn_level_bwd_t *, void *) = nullptr;
   const char *(*last_error)(void) = nullptr;
   bool device = false;   // true: the HIP library (tensors must be on a cuda device)
 };
@@ -324,6 +326,58 @@ void gcn_level(int64_t lib, int64_t stream, at::TensorList x, at::TensorList adj
 void gcn_level_meta(int64_t, int64_t, at::TensorList, at::TensorList, const c10::List<OT> &, at::TensorList, at::TensorList, at::TensorList, at::TensorList,
                     at::IntArrayRef) {}
 
+// the backward of such a level in one launch: d_b[i] = sum_rows dZ, d_w[i] = dZ^T x_agg[i], d_x[i] = adj[i]^T (dZ w[i]) with
+// dZ = d_out[i] * act[i]'(out[i]); the lists of optional tensors are empty or hold one entry per layer (None: not wanted)
+// == truss_gcn_level_backward
+void gcn_level_backward(int64_t lib, int64_t stream, at::TensorList adj, at::TensorList w, at::IntArrayRef act, at::TensorList d_out,
+                        at::TensorList out, const c10::List<OT> &x_agg, const c10::List<OT> &d_w, const c10::List<OT> &d_b,
+                        const c10::List<OT> &d_x) {
+  const Backend &b = backend(lib);
+  TORCH_CHECK(b.gcn_level_bwd, "truss_mi355: the bound native library has no truss_gcn_level_backward");
+  const size_t L = d_out.size();
+  auto per_layer = [L](const c10::List<OT> &l) { return l.empty() || l.size() == L; };
+  TORCH_CHECK(adj.size() == L && w.size() == L && act.size() == L && out.size() == L && per_layer(x_agg) && per_layer(d_w) && per_layer(d_b) &&
+                  per_layer(d_x),
+              "truss_mi355: gcn_level_backward takes one entry per layer in every list");
+  std::vector<truss_gcn_layer_args_t> args(L);
+  std::vector<truss_gcn_level_bwd_t> bw(L);
+  auto opt = [](const c10::List<OT> &l, size_t i) -> OT { return l.empty() ? OT() : l.get(i); };
+  for (size_t i = 0; i < L; ++i) {
+    TORCH_CHECK(d_out[i].dim() == 3 && w[i].dim() == 2 && out[i].sizes() == d_out[i].sizes(),
+                "truss_mi355: d_out / out [B, N, C] of equal shape, w [C, K]");
+    const int64_t B = d_out[i].size(0), N = d_out[i].size(1), C = d_out[i].size(2), K = w[i].size(1);
+    TORCH_CHECK(w[i].size(0) == C, "truss_mi355: gcn_level_backward shapes do not match");
+    TORCH_CHECK((adj[i].dim() == 2 || adj[i].dim() == 3) && adj[i].size(-1) == N && adj[i].size(-2) == N && (adj[i].dim() == 2 || adj[i].size(0) == B),
+                "truss_mi355: adj must be [N, N] or [B, N, N]");
+    truss_gcn_layer_args_t &a = args[i];
+    a = truss_gcn_layer_args_t{};
+    a.struct_size = sizeof a;
+    a.n_batch = (int32_t)B;
+    a.n_nodes = (int32_t)N;
+    a.k_in = (int32_t)K;
+    a.c_out = (int32_t)C;
+    a.act = (int32_t)act[i];
+    a.adj = ptr<const float>(b, adj[i], at::kFloat, "adj");
+    a.a_batch_stride = adj[i].dim() == 3 ? N * N : 0;
+    a.w = ptr<const float>(b, w[i], at::kFloat, "w");
+    truss_gcn_level_bwd_t &g = bw[i];
+    g = truss_gcn_level_bwd_t{};
+    g.d_out = ptr<const float>(b, d_out[i], at::kFloat, "d_out");
+    g.out = ptr<const float>(b, out[i], at::kFloat, "out");
+    g.x_agg = ptr<const float>(b, opt(x_agg, i), at::kFloat, "x_agg", B * N * K);
+    const OT dw = opt(d_w, i), db = opt(d_b, i), dx = opt(d_x, i);
+    TORCH_CHECK(!(dw.has_value() && dw->defined()) || dw->numel() == C * K, "truss_mi355: d_w[i] must hold C * K elements");
+    TORCH_CHECK(!(db.has_value() && db->defined()) || db->numel() == C, "truss_mi355: d_b[i] must hold C elements");
+    TORCH_CHECK(!(dx.has_value() && dx->defined()) || dx->numel() == B * N * K, "truss_mi355: d_x[i] must hold B * N * K elements");
+    g.d_w = ptr<float>(b, dw, at::kFloat, "d_w");
+    g.d_b = ptr<float>(b, db, at::kFloat, "d_b");
+    g.d_x = ptr<float>(b, dx, at::kFloat, "d_x");
+  }
+  check_rc(b, b.gcn_level_bwd(args.data(), (int32_t)L, bw.data(), (void *)stream), "truss_gcn_level_backward");
+}
+void gcn_level_backward_meta(int64_t, int64_t, at::TensorList, at::TensorList, at::IntArrayRef, at::TensorList, at::TensorList, const c10::List<OT> &,
+                             const c10::List<OT> &, const c10::List<OT> &, const c10::List<OT> &) {}
+
 // w [C, K] float32 -> out [3, 224, KP] int16 (bfloat16 bit patterns, zero rows / columns beyond C / K): the exact three-term split of the bf16x3 path == truss_gcn_split_w
 void gcn_split_w(int64_t lib, int64_t stream, const at::Tensor &w, const at::Tensor &out) {
   const Backend &b = backend(lib);
@@ -339,7 +393,8 @@ void gcn_split_meta(int64_t, int64_t, const at::Tensor &, const at::Tensor &) {}
 
 // Bind the entry points of a loaded native library (addresses from ctypes) under a small index.
 extern "C" int truss_torch_bind(int lib, void *step_fn, void *rollout_fn, void *obs_fn, void *front_fn, void *gcn_fn, void *gcn_sparse_fn,
-                                void *gcn_layer_fn, void *gcn_split_fn, void *gcn_level_fn, void *last_error_fn, int is_device) {
+                                void *gcn_layer_fn, void *gcn_split_fn, void *gcn_level_fn, void *gcn_level_bwd_fn, void *last_error_fn,
+                                int is_device) {
   if (lib < 0 || lib >= (int)g_backends.size() || !step_fn) return -1;
   Backend &b = g_backends[lib];
   b.step = (decltype(b.step))step_fn;
@@ -351,6 +406,7 @@ extern "C" int truss_torch_bind(int lib, void *step_fn, void *rollout_fn, void *
   b.gcn_layer = (decltype(b.gcn_layer))gcn_layer_fn;
   b.gcn_split = (decltype(b.gcn_split))gcn_split_fn;
   b.gcn_level = (decltype(b.gcn_level))gcn_level_fn;
+  b.gcn_level_bwd = (decltype(b.gcn_level_bwd))gcn_level_bwd_fn;   // (may be null: a library without the entry)
   b.last_error = (decltype(b.last_error))last_error_fn;
   b.device = is_device != 0;
   return 0;
@@ -379,6 +435,8 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("gcn_split_w(int lib, int stream, Tensor w, Tensor(a!) out) -> ()");
   m.def("gcn_level(int lib, int stream, Tensor[] x, Tensor[] adj, Tensor?[] nbr, Tensor[] w, Tensor[] bias, Tensor(a!)[] out, Tensor(b!)[] x_agg, "
         "int[] act) -> ()");
+  m.def("gcn_level_backward(int lib, int stream, Tensor[] adj, Tensor[] w, int[] act, Tensor[] d_out, Tensor[] out, Tensor?[] x_agg, "
+        "Tensor(a!)?[] d_w, Tensor(b!)?[] d_b, Tensor(c!)?[] d_x) -> ()");
 }
 TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) {   // the emulator library of the test-suite binds here
   m.impl("step", step);
@@ -390,6 +448,7 @@ TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) {   // the emulator library of the test-
   m.impl("gcn_layer", gcn_layer);
   m.impl("gcn_split_w", gcn_split_w);
   m.impl("gcn_level", gcn_level);
+  m.impl("gcn_level_backward", gcn_level_backward);
 }
 TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) {  // = HIP on ROCm: the product library
   m.impl("step", step);
@@ -401,6 +460,7 @@ TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) {  // = HIP on ROCm: the product librar
   m.impl("gcn_layer", gcn_layer);
   m.impl("gcn_split_w", gcn_split_w);
   m.impl("gcn_level", gcn_level);
+  m.impl("gcn_level_backward", gcn_level_backward);
 }
 TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {  // tracing: every operator only mutates its outputs
   m.impl("step", step_meta);
@@ -412,4 +472,5 @@ TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {  // tracing: every operator only muta
   m.impl("gcn_layer", gcn_layer_meta);
   m.impl("gcn_split_w", gcn_split_meta);
   m.impl("gcn_level", gcn_level_meta);
+  m.impl("gcn_level_backward", gcn_level_backward_meta);
 }

@@ -143,7 +143,8 @@ class multimodes_critic(nn.Module):
 #             csrc/truss_gcn.h: MFMA, every layer of the level a slice of the grid) -- or, per group of equally shaped layers, two
 #             batched GEMMs over stacked operands (CPU, and the reference for the kernel);
 #   backward  dZ = dOut * act'(out);  db = sum dZ;  dW = dZ^T X'  (one batched GEMM per group: X' was kept);
-#             dX = A^T (dZ W)  (two batched GEMMs, only where an input asks for it).
+#             dX = A^T (dZ W)  (two batched GEMMs, only where an input asks for it) -- or, where `set_level_backward` installed
+#             it, one fused launch for the whole level (truss_gcn_level_backward, csrc/truss_gcn_level_bwd.h).
 # The networks are written as generators that yield one level's requests at a time (`_actor_steps`, `_critic_steps`);
 # `run_networks` steps several of them in lockstep and hands each level of all of them to `gcn_level` together.  Same parameters
 # (the modules' own tensors: state_dict, checkpoints and the per-layer `forward` are untouched), same mathematics in a different
@@ -159,6 +160,17 @@ def set_level_forward(fn, device_type="cuda"):
         _LEVEL_FORWARD.pop(device_type, None)
     else:
         _LEVEL_FORWARD[device_type] = fn
+
+
+_LEVEL_BACKWARD = {}       # device type -> callable(groups, douts, outs, xaggs, ws, need) -> (dx, dw, db) or None (truss_mi355.marl.level_backward)
+
+
+def set_level_backward(fn, device_type="cuda"):
+    """Install (or, with None, remove) the fused level-backward for tensors of `device_type`; see `_GcnLevel.backward` for its contract."""
+    if fn is None:
+        _LEVEL_BACKWARD.pop(device_type, None)
+    else:
+        _LEVEL_BACKWARD[device_type] = fn
 
 
 class _Group:
@@ -227,6 +239,17 @@ class _GcnLevel(torch.autograd.Function):
         saved = ctx.saved_tensors
         outs, xaggs, ws = saved[:G], saved[G:2 * G], saved[2 * G:]
         need = ctx.needs_input_grad
+        # the fused backward, where one is installed: fn(groups, douts, outs, xaggs, ws, need) with douts / outs [n, B, N, C] and
+        # xaggs [n, B N, K] per group (douts[gi] None: nothing flows back into that group), ws the L weights and need =
+        # needs_input_grad of apply((plan), *xs, *ws, *bs) -- need[1 + i], need[1 + L + i], need[1 + 2 L + i] for x, w, b of request i.
+        # It returns (dx, dw, db), lists of length L in request order (None where nothing is needed; the pieces of a group are the
+        # `unbind` of ONE stacked tensor per quantity), or None to leave the whole level to the library path below.
+        fused = _LEVEL_BACKWARD.get(outs[0].device.type) if G else None
+        if fused is not None:
+            res = fused(groups, douts, outs, xaggs, ws, need)
+            if res is not None:
+                dx, dw, db = res
+                return (None, *dx, *dw, *db)
         dx, dw, db = [None] * L, [None] * L, [None] * L
         for gi, g in enumerate(groups):
             need_w = any(need[1 + L + i] or need[1 + 2 * L + i] for i in g.idx)

@@ -103,6 +103,10 @@ class TrussLib:
         d.truss_gcn_layer.argtypes = [_vp, _vp]
         d.truss_gcn_level.restype = C.c_int
         d.truss_gcn_level.argtypes = [_vp, C.c_int32, _vp, _vp]
+        self.has_level_backward = hasattr(d, "truss_gcn_level_backward")     # (optional: the CPU lane emulator does not export it)
+        if self.has_level_backward:
+            d.truss_gcn_level_backward.restype = C.c_int
+            d.truss_gcn_level_backward.argtypes = [_vp, C.c_int32, _vp, _vp]
         d.truss_gcn_split_w.restype = C.c_int
         d.truss_gcn_split_w.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
         d.truss_gcn_aggregate_sparse.restype = C.c_int

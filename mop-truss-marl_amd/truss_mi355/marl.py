@@ -253,6 +253,67 @@ def level_forward(lib):
     return run
 
 
+def level_backward(lib):
+    """The fused backward of a whole level of GCN layers (`truss_gcn_level_backward`, csrc/truss_gcn_level_bwd.h: one launch for
+    every layer of every group that something flows back into) in the shape truss2D_RL._GcnLevel.backward asks for:
+    callable(groups, douts, outs, xaggs, ws, need) -> (dx, dw, db), lists in request order whose entries are the `unbind` pieces of
+    one stacked tensor per group and quantity ([n, B, N, K], [n, C, K], [n, C]), or None when a group is outside the kernel's
+    envelope (the caller then runs the level's backward as batched library GEMMs).  Installed by
+    BatchedMARL(level_backward="hip") on the GPU (`truss2D_RL.set_level_backward`)."""
+    from . import ops
+    code = {None: 0, "relu": 1, "sigmoid": 2}
+
+    def run(groups, douts, outs, xaggs, ws, need):
+        L = len(ws)
+        todo = []
+        for gi, g in enumerate(groups):
+            need_w = any(need[1 + L + i] or need[1 + 2 * L + i] for i in g.idx)
+            need_x = any(need[1 + i] for i in g.idx)
+            if douts[gi] is None or not (need_w or need_x):
+                continue                                                             # no slices in the launch
+            (B, N, K), C = g.shape, outs[gi].shape[-1]
+            if N > 64 or C > 224 or K > 256 or outs[gi].dtype != torch.float32 or douts[gi].dtype != torch.float32 \
+                    or (need_w and xaggs[gi] is None):                              # outside the kernel's envelope
+                return None
+            todo.append((gi, g, need_w, need_x))
+        dx, dw, db = [None] * L, [None] * L, [None] * L
+        if not todo:
+            return dx, dw, db
+        ADJ, W, ACT, DOUT, OUT, XAGG, DW, DB, DX = [], [], [], [], [], [], [], [], []
+        for gi, g, need_w, need_x in todo:
+            n, (B, N, K), C = len(g.idx), g.shape, outs[gi].shape[-1]
+            dev = outs[gi].device
+            d = douts[gi].contiguous()
+            gw = torch.empty((n, C, K), dtype=torch.float32, device=dev) if need_w else None
+            gb = torch.empty((n, C), dtype=torch.float32, device=dev) if need_w else None
+            gx = torch.empty((n, B, N, K), dtype=torch.float32, device=dev) if need_x else None
+            for j, i in enumerate(g.idx):
+                a = g.adjs[j]
+                if a.dim() == 3 and (a.shape[0] == 1 or a.stride(0) == 0):
+                    a = a[0]
+                ADJ.append(a.contiguous())
+                W.append(ws[i].detach())
+                ACT.append(code[g.act])
+                DOUT.append(d[j])
+                OUT.append(outs[gi][j])
+                XAGG.append(xaggs[gi][j] if need_w else None)
+                DW.append(gw[j] if need_w else None)
+                DB.append(gb[j] if need_w else None)
+                DX.append(gx[j] if need_x else None)
+            if need_w:
+                for i, pw, pb in zip(g.idx, gw.unbind(0), gb.unbind(0)):
+                    dw[i], db[i] = pw, pb
+            if need_x:
+                for i, piece in zip(g.idx, gx.unbind(0)):
+                    dx[i] = piece                          # (one tensor passed for several layers: autograd adds per argument)
+        ops.call(ops.namespace().gcn_level_backward, ops.bind(lib), ops.stream_of(OUT[0].device), ADJ, W, ACT, DOUT, OUT, XAGG, DW, DB, DX)
+        return dx, dw, db
+    return run
+
+
+_level_backward_hook = level_backward        # (BatchedMARL's argument of the same name shadows the function)
+
+
 def gcn_layer_supported(n_nodes, c_out, nbr):
     """shapes the fused layer kernel takes (include/truss_mi355.h); anything else goes through library GEMM + aggregation kernels"""
     return c_out <= 224 and n_nodes <= 256 and ((nbr is not None and nbr.shape[1] <= 16) or (nbr is None and n_nodes <= 64))
@@ -386,7 +447,12 @@ class BatchedMARL:
 
     def __init__(self, topo: TrussTopology, n_envs: int, maddpg, *, max_front: int | None = None, lib=None, device=None,
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
-                 pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None):
+                 pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None,
+                 level_backward: str | None = None):
+        """level_backward: how the update differentiates a level of GCN layers on the GPU -- "library" (batched library GEMMs, the
+        default) or "hip" (one `truss_gcn_level_backward` launch per level); None: "hip" if the environment has
+        TRUSS_LEVEL_BACKWARD=1, else "library".  The choice is installed process-wide for cuda tensors (like the level forward)
+        and is part of an update graph from the moment it is captured."""
         if game not in ("train", "test"):
             raise ValueError(f"game must be 'train' or 'test', got {game!r}")
         if game == "test" and len(topo.sym_nodes) == 0:
@@ -415,6 +481,14 @@ class BatchedMARL:
         if self.device.type == "cuda" and os.environ.get("TRUSS_LEVEL_FORWARD", "1") != "0":
             import truss2D_RL
             truss2D_RL.set_level_forward(level_forward(self.lib), "cuda")   # the update's forward passes: one launch per level
+        if level_backward is None:
+            level_backward = "hip" if os.environ.get("TRUSS_LEVEL_BACKWARD", "0") == "1" else "library"
+        if level_backward not in ("library", "hip"):
+            raise ValueError(f"level_backward must be 'library' or 'hip', got {level_backward!r}")
+        self.level_backward = level_backward
+        if self.device.type == "cuda":
+            import truss2D_RL
+            truss2D_RL.set_level_backward(_level_backward_hook(self.lib) if level_backward == "hip" else None, "cuda")
         dev, B, P, N, E = self.device, self.B, self.P, topo.N, topo.E
         A_n, mask = topo.normalized_adjacency()
         self.A_n = torch.tensor(A_n, device=dev)[None]
