@@ -355,6 +355,44 @@ int truss_gcn_level_backward(const truss_gcn_layer_args_t *layers, int32_t n_lay
  * three-term split the bf16x3 path of truss_gcn_layer reads.  Once per weight version; device pointers, 16-byte aligned output. */
 int truss_gcn_split_w(const float *w, int32_t c_out, int32_t k_in, uint16_t *w_bf16x3, void *stream);
 
+/* ---- replay buffer: append and sample, every field of a transition in one launch -------------------------------
+ * replaces: MADDPG.remember (truss2D_RL.py:458-460: one deque append per transition) and the batch assembly at the top of
+ * MADDPG.train (truss2D_RL.py:463 onward: random.sample + one np.array per field), for a replay that lives in device memory as
+ * one ring tensor per FIELD of a transition ([capacity][row]; today 27 fields: 6 observation tensors x (state + 3 next states),
+ * the two action tensors and the rewards).  Data is only moved: bit patterns survive (NaN payloads, -0.0).  A field is
+ *   plain    (nbr == NULL): a ring row of parts x part_len floats.  The tensor outside the ring may be strided in two levels --
+ *            rows ext_row_stride floats apart, the parts of a row ext_part_stride apart -- so that a permuted view [K, 3, N, c] of
+ *            an agent-major [3, K, N, c] tensor is read in place, the accepted rows only;
+ *   pattern  (nbr != NULL): a dense [n][n] matrix outside the ring, [n][k_nbr] inside it, through the table nbr[n][k_nbr] of the
+ *            columns that may be non-zero in each row (as for truss_gcn_aggregate_sparse: int16, ascending, -1 = unused slot,
+ *            k_nbr <= 16).  Unused slots are stored as +0.0.  Lossless iff the matrix is zero outside the table.
+ * truss_replay_scatter (append): for r < k, ring row (head + r) % capacity of every field <- row rows[group][r] of its `ext`
+ *   (rows: int64 [4][k]: list 0 for the state's fields, 1 + a for agent a's next state; an index outside [0, ext_rows) skips the row).
+ * truss_replay_gather (sample): for r < batch, row r of every field's `ext` <- ring row idx[r] (outside [0, capacity): skipped).  A
+ *   pattern field writes the WHOLE dense row: zeros, then the listed entries.
+ * Rows move in 16-byte pieces where addresses and lengths allow, element by element otherwise.  Every output element has one
+ * owner (no atomics); ring rows that are not addressed keep their contents.  More than 32 fields are run as consecutive launches.
+ * k == 0 / batch == 0 / n_fields == 0: nothing to do.  TRUSS_EINVAL: a NULL pointer, capacity < 1, head outside [0, capacity),
+ * k > capacity, bad sizes; TRUSS_EUNSUPPORTED: k_nbr > 16 (or rows x row pieces >= 2^31 in one field); nothing is written then.
+ * The library neither allocates nor synchronises: both entries may be captured in a hipGraph.  Device pointers.  Optional
+ * symbols: a library of this ABI version may lack them. */
+typedef struct truss_replay_field {
+  float *ring;              /* [capacity][parts * part_len] (plain) or [capacity][n][k_nbr] (pattern), contiguous */
+  float *ext;               /* the tensor outside the ring: read by scatter (never written), written by gather */
+  const int16_t *nbr;       /* NULL: plain field */
+  int64_t ext_rows;         /* rows of ext */
+  int64_t ext_row_stride;   /* floats between rows of ext */
+  int64_t ext_part_stride;  /* plain: floats between the parts of one row of ext (not read when parts == 1) */
+  int32_t parts, part_len;  /* plain */
+  int32_t n, k_nbr;         /* pattern; the dense matrix itself is contiguous */
+  int32_t group;            /* scatter: the list of `rows` (0..3) this field takes its source rows from */
+  int32_t reserved;
+} truss_replay_field_t;
+int truss_replay_scatter(const truss_replay_field_t *fields, int32_t n_fields, const int64_t *rows, int32_t k, int64_t head,
+                         int64_t capacity, void *stream);
+int truss_replay_gather(const truss_replay_field_t *fields, int32_t n_fields, const int64_t *idx, int32_t batch, int64_t capacity,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -792,6 +792,7 @@ extern "C" int truss_debug_stamps(unsigned long long *out16) {
 #include "truss_gcn.h"
 #include "truss_gcn_level.h"
 #include "truss_gcn_level_bwd.h"
+#include "truss_replay.h"
 
 #include "truss_front.h"
 extern "C" int truss_front(const truss_front_args_t *a, void *stream) {

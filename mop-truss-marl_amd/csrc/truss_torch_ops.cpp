@@ -1,7 +1,7 @@
 // truss_torch_ops.cpp -- PyTorch custom operators in front of the C ABI of include/truss_mi355.h.
 //
 //   torch.ops.truss_mi355.step / rollout / obs / front / gcn_aggregate / gcn_aggregate_sparse / gcn_layer / gcn_level /
-//   gcn_level_backward
+//   gcn_level_backward / replay_scatter / replay_gather
 //
 // The reference's hot path runs inside TensorFlow ops on its side of the loop (truss2D_RL.py:328-354); here the env
 // step itself is an operator of the host framework: tensors in, tensors mutated in place, launched on the stream the
@@ -33,6 +33,8 @@ struct Backend {
   int (*gcn_split)(const float *, int32_t, int32_t, uint16_t *, void *) = nullptr;
   int (*gcn_level)(const truss_gcn_layer_args_t *, int32_t, float *const *, void *) = nullptr;
   int (*gcn_level_bwd)(const truss_gcn_layer_args_t *, int32_t, const truss_gcn_level_bwd_t *, void *) = nullptr;
+  int (*replay_scatter)(const truss_replay_field_t *, int32_t, const int64_t *, int32_t, int64_t, int64_t, void *) = nullptr;
+  int (*replay_gather)(const truss_replay_field_t *, int32_t, const int64_t *, int32_t, int64_t, void *) = nullptr;
   const char *(*last_error)(void) = nullptr;
   bool device = false;   // true: the HIP library (tensors must be on a cuda device)
 };
@@ -389,12 +391,99 @@ void gcn_split_w(int64_t lib, int64_t stream, const at::Tensor &w, const at::Ten
 }
 void gcn_split_meta(int64_t, int64_t, const at::Tensor &, const at::Tensor &) {}
 
+// float32 tensor of the bound library's device that need not be contiguous (a view read in place)
+float *view_ptr(const Backend &b, const at::Tensor &t, const char *name) {
+  TORCH_CHECK(t.scalar_type() == at::kFloat, "truss_mi355: ", name, " must be ", at::kFloat, ", got ", t.scalar_type());
+  TORCH_CHECK(b.device ? t.is_cuda() : t.is_cpu(), "truss_mi355: ", name, " is on ", t.device(), ", the bound library needs ",
+              b.device ? "a cuda (ROCm) device" : "the cpu");
+  return (float *)t.data_ptr();
+}
+bool dense_from(const at::Tensor &t, int64_t d0) {   // dims d0.. laid out contiguously
+  int64_t want = 1;
+  for (int64_t d = t.dim() - 1; d >= d0; --d) {
+    if (t.size(d) != 1 && t.stride(d) != want) return false;
+    want *= t.size(d);
+  }
+  return true;
+}
+// descriptor of one field: ring [capacity, ...] contiguous, ext [rows, ...] of the same row shape (pattern: [rows, n, n] against
+// ring [capacity, n, k_nbr]); a plain ext may be strided over its rows and over dim 1 (a permuted view)
+truss_replay_field_t replay_field(const Backend &b, const at::Tensor &ring, const at::Tensor &ext, const OT &nbr, int64_t capacity, int64_t group) {
+  truss_replay_field_t f{};
+  TORCH_CHECK(ring.dim() >= 1 && ring.size(0) == capacity && capacity >= 1, "truss_mi355: a replay ring tensor must be [capacity, ...]");
+  TORCH_CHECK(ext.dim() == ring.dim(), "truss_mi355: replay field: ring and outside tensor must have the same number of dims");
+  f.ring = ptr<float>(b, ring, at::kFloat, "ring");
+  f.ext = view_ptr(b, ext, "replay field");
+  f.ext_rows = ext.size(0);
+  f.ext_row_stride = ext.size(0) > 1 ? ext.stride(0) : 0;
+  f.group = (int32_t)group;
+  const int64_t row = ring.numel() / capacity;
+  if (nbr.has_value() && nbr->defined()) {
+    TORCH_CHECK(ring.dim() == 3 && nbr->dim() == 2 && nbr->size(0) == ring.size(1) && nbr->size(1) == ring.size(2) && ext.size(1) == ring.size(1) &&
+                    ext.size(2) == ring.size(1) && dense_from(ext, 1),
+                "truss_mi355: replay pattern field: ring [capacity, n, k_nbr], nbr [n, k_nbr], outside tensor [rows, n, n] with contiguous matrices");
+    f.nbr = ptr<const int16_t>(b, *nbr, at::kShort, "nbr");
+    f.n = (int32_t)ring.size(1);
+    f.k_nbr = (int32_t)ring.size(2);
+  } else {
+    TORCH_CHECK(ext.sizes().slice(1) == ring.sizes().slice(1), "truss_mi355: replay plain field: ring and outside tensor rows differ in shape");
+    TORCH_CHECK(row >= 1 && row <= INT32_MAX, "truss_mi355: replay plain field: bad row length");
+    if (dense_from(ext, 1)) {
+      f.parts = 1;
+      f.part_len = (int32_t)row;
+    } else {
+      TORCH_CHECK(ext.dim() >= 2 && dense_from(ext, 2) && ext.stride(1) >= 0,
+                  "truss_mi355: replay plain field: the outside tensor may be strided over dims 0 and 1 only");
+      f.parts = (int32_t)ext.size(1);
+      f.part_len = (int32_t)(row / ext.size(1));
+      f.ext_part_stride = ext.stride(1);
+    }
+  }
+  TORCH_CHECK(f.ext_row_stride >= 0, "truss_mi355: replay field: negative stride");
+  return f;
+}
+
+// append: ring row (head + r) % capacity of every field <- row rows[group[i]][r] of src[i], r < k == truss_replay_scatter
+void replay_scatter(int64_t lib, int64_t stream, at::TensorList ring, at::TensorList src, const c10::List<OT> &nbr, at::IntArrayRef group,
+                    const at::Tensor &rows, int64_t k, int64_t head, int64_t capacity) {
+  const Backend &b = backend(lib);
+  TORCH_CHECK(b.replay_scatter, "truss_mi355: the bound native library has no truss_replay_scatter");
+  const size_t F = ring.size();
+  TORCH_CHECK(src.size() == F && nbr.size() == F && group.size() == F, "truss_mi355: replay_scatter takes one entry per field in every list");
+  TORCH_CHECK(k >= 0 && k <= INT32_MAX && rows.dim() == 2 && rows.size(0) == 4 && rows.size(1) == k, "truss_mi355: rows must be [4, k]");
+  std::vector<truss_replay_field_t> f(F);
+  for (size_t i = 0; i < F; ++i) f[i] = replay_field(b, ring[i], src[i], nbr.get(i), capacity, group[i]);
+  const int64_t *pr = ptr<const int64_t>(b, rows, at::kLong, "rows");
+  check_rc(b, b.replay_scatter(f.data(), (int32_t)F, pr, (int32_t)k, head, capacity, (void *)stream), "truss_replay_scatter");
+}
+void replay_scatter_meta(int64_t, int64_t, at::TensorList, at::TensorList, const c10::List<OT> &, at::IntArrayRef, const at::Tensor &, int64_t, int64_t,
+                         int64_t) {}
+
+// sample: row r of out[i] <- ring row idx[r] of every field (a pattern field: the whole dense matrix) == truss_replay_gather
+void replay_gather(int64_t lib, int64_t stream, at::TensorList ring, at::TensorList out, const c10::List<OT> &nbr, const at::Tensor &idx,
+                   int64_t capacity) {
+  const Backend &b = backend(lib);
+  TORCH_CHECK(b.replay_gather, "truss_mi355: the bound native library has no truss_replay_gather");
+  const size_t F = ring.size();
+  TORCH_CHECK(out.size() == F && nbr.size() == F, "truss_mi355: replay_gather takes one entry per field in every list");
+  TORCH_CHECK(idx.dim() == 1 && idx.numel() <= INT32_MAX, "truss_mi355: idx must be [batch]");
+  const int64_t batch = idx.numel();
+  std::vector<truss_replay_field_t> f(F);
+  for (size_t i = 0; i < F; ++i) {
+    TORCH_CHECK(out[i].dim() >= 1 && out[i].size(0) == batch, "truss_mi355: replay_gather outputs must be [batch, ...]");
+    f[i] = replay_field(b, ring[i], out[i], nbr.get(i), capacity, 0);
+  }
+  const int64_t *pi = ptr<const int64_t>(b, idx, at::kLong, "idx");
+  check_rc(b, b.replay_gather(f.data(), (int32_t)F, pi, (int32_t)batch, capacity, (void *)stream), "truss_replay_gather");
+}
+void replay_gather_meta(int64_t, int64_t, at::TensorList, at::TensorList, const c10::List<OT> &, const at::Tensor &, int64_t) {}
+
 }  // namespace
 
 // Bind the entry points of a loaded native library (addresses from ctypes) under a small index.
 extern "C" int truss_torch_bind(int lib, void *step_fn, void *rollout_fn, void *obs_fn, void *front_fn, void *gcn_fn, void *gcn_sparse_fn,
-                                void *gcn_layer_fn, void *gcn_split_fn, void *gcn_level_fn, void *gcn_level_bwd_fn, void *last_error_fn,
-                                int is_device) {
+                                void *gcn_layer_fn, void *gcn_split_fn, void *gcn_level_fn, void *gcn_level_bwd_fn, void *replay_scatter_fn,
+                                void *replay_gather_fn, void *last_error_fn, int is_device) {
   if (lib < 0 || lib >= (int)g_backends.size() || !step_fn) return -1;
   Backend &b = g_backends[lib];
   b.step = (decltype(b.step))step_fn;
@@ -407,6 +496,8 @@ extern "C" int truss_torch_bind(int lib, void *step_fn, void *rollout_fn, void *
   b.gcn_split = (decltype(b.gcn_split))gcn_split_fn;
   b.gcn_level = (decltype(b.gcn_level))gcn_level_fn;
   b.gcn_level_bwd = (decltype(b.gcn_level_bwd))gcn_level_bwd_fn;   // (may be null: a library without the entry)
+  b.replay_scatter = (decltype(b.replay_scatter))replay_scatter_fn;   // (these two as well)
+  b.replay_gather = (decltype(b.replay_gather))replay_gather_fn;
   b.last_error = (decltype(b.last_error))last_error_fn;
   b.device = is_device != 0;
   return 0;
@@ -437,6 +528,9 @@ TORCH_LIBRARY(truss_mi355, m) {
         "int[] act) -> ()");
   m.def("gcn_level_backward(int lib, int stream, Tensor[] adj, Tensor[] w, int[] act, Tensor[] d_out, Tensor[] out, Tensor?[] x_agg, "
         "Tensor(a!)?[] d_w, Tensor(b!)?[] d_b, Tensor(c!)?[] d_x) -> ()");
+  m.def("replay_scatter(int lib, int stream, Tensor(a!)[] ring, Tensor[] src, Tensor?[] nbr, int[] group, Tensor rows, int k, int head, "
+        "int capacity) -> ()");
+  m.def("replay_gather(int lib, int stream, Tensor[] ring, Tensor(a!)[] out, Tensor?[] nbr, Tensor idx, int capacity) -> ()");
 }
 TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) {   // the emulator library of the test-suite binds here
   m.impl("step", step);
@@ -449,6 +543,8 @@ TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) {   // the emulator library of the test-
   m.impl("gcn_split_w", gcn_split_w);
   m.impl("gcn_level", gcn_level);
   m.impl("gcn_level_backward", gcn_level_backward);
+  m.impl("replay_scatter", replay_scatter);
+  m.impl("replay_gather", replay_gather);
 }
 TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) {  // = HIP on ROCm: the product library
   m.impl("step", step);
@@ -461,6 +557,8 @@ TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) {  // = HIP on ROCm: the product librar
   m.impl("gcn_split_w", gcn_split_w);
   m.impl("gcn_level", gcn_level);
   m.impl("gcn_level_backward", gcn_level_backward);
+  m.impl("replay_scatter", replay_scatter);
+  m.impl("replay_gather", replay_gather);
 }
 TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {  // tracing: every operator only mutates its outputs
   m.impl("step", step_meta);
@@ -473,4 +571,6 @@ TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {  // tracing: every operator only muta
   m.impl("gcn_split_w", gcn_split_meta);
   m.impl("gcn_level", gcn_level_meta);
   m.impl("gcn_level_backward", gcn_level_backward_meta);
+  m.impl("replay_scatter", replay_scatter_meta);
+  m.impl("replay_gather", replay_gather_meta);
 }

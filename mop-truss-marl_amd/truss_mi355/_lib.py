@@ -107,6 +107,13 @@ class TrussLib:
         if self.has_level_backward:
             d.truss_gcn_level_backward.restype = C.c_int
             d.truss_gcn_level_backward.argtypes = [_vp, C.c_int32, _vp, _vp]
+        # (optional as well: the replay buffer's fused append / sample)
+        self.has_replay_ops = hasattr(d, "truss_replay_scatter") and hasattr(d, "truss_replay_gather")
+        if self.has_replay_ops:
+            d.truss_replay_scatter.restype = C.c_int
+            d.truss_replay_scatter.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int64, C.c_int64, _vp]   # (truss_replay_field_t *: filled by the operators)
+            d.truss_replay_gather.restype = C.c_int
+            d.truss_replay_gather.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int64, _vp]
         d.truss_gcn_split_w.restype = C.c_int
         d.truss_gcn_split_w.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
         d.truss_gcn_aggregate_sparse.restype = C.c_int
