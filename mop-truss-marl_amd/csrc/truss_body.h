@@ -200,7 +200,7 @@ struct StepLane {
   // per-env scalars
   double max_def, load_x, load_y;
   float ymax32, dmin32, ymd32, int1, int2;
-  int is_roof, heads;
+  int is_roof;
   // element stash
   double ek[EPL], ec[EPL], es[EPL], ei[EPL];
   // solver window
@@ -224,6 +224,14 @@ struct StepLane {
   TRUSS_HD float *geosh(const TopoDev &T) { return (float *)(L + T.o_geo); }
   TRUSS_HD float *tac(const TopoDev &T) { return (float *)(L + T.o_tac); }
   TRUSS_HD int32_t *secsh(const TopoDev &T) { return (int32_t *)(L + T.o_sec); }
+  // the env's symmetry coin, parked by phase_stage: the last word of the 64 bytes of bank-stagger padding that end every env
+  // region (truss_host.h: env_stride), which no row and no feature bank reaches.  Like the env parameters it is a per-env
+  // constant of a launch: the persistent rollout stages it in its first step only.
+  TRUSS_HD int32_t *coinsh(const TopoDev &T) { return (int32_t *)(L + T.env_stride - 4); }
+  // the coin has a meaning only where phase_sym_nodes runs (wave-uniform)
+  TRUSS_HD static bool coin_used(const TopoDev &T, const StepArgsDev &A) {
+    return T.n_sym_nodes > 0 && !(A.flags & TB_NO_DECODE) && A.coin;
+  }
   TRUSS_HD double *evsh(const TopoDev &T) { return (double *)(L + T.o_ev); }
   TRUSS_HD const int16_t *t_conn(const TopoDev &T) const { return TB_TAB(int16_t, TB, T.f_conn); }
   TRUSS_HD const int16_t *t_pairs(const TopoDev &T) const { return TB_TAB(int16_t, TB, T.f_pairs); }
@@ -359,6 +367,9 @@ struct StepLane {
         row_load<2 * NIT>(A.a_geo + bn * 2, 2 * nn, vg);
         row_load<3 * NIT>(A.a_topo + bn * 3, 3 * nn, va);
       }
+      const bool coin = coin_used(T, A);
+      int cb = 0;
+      if (coin) cb = A.coin[envc];   // in flight with the rows (envc is clamped); first used by the LDS store below
       band_clear(T);   // independent of the loads in flight: its LDS stores overlap the HBM latency
       {
         tb_u4 *d4 = (tb_u4 *)TB;
@@ -377,6 +388,7 @@ struct StepLane {
         row_store<2 * NIT>(geosh(T), 2 * nn, vg);
         row_store<3 * NIT>(tac(T), 3 * nn, va);
       }
+      if (coin) *coinsh(T) = cb;     // every lane of the env stores the same word
     }
   }
 
@@ -384,10 +396,9 @@ struct StepLane {
     const size_t bn = (size_t)envc * T.N, be = (size_t)envc * T.E;
     const bool decode = !(A.flags & TB_NO_DECODE);
     const bool fast = (T.N & 3) == 0 && (T.E & 3) == 0 && T.N <= NCAP && T.E <= ECAP && T.blob_bytes <= BIT_BIG * 64 * 16;
-    heads = A.coin ? (A.coin[envc] != 0) : 0;
     if (rs_first_step != 0) {
-      // persistent rollout, a step after the first: topology tables, constants and the design (the previous step's result)
-      // are in LDS, this step's actions were parked there by rollout_stash -- nothing to fetch
+      // persistent rollout, a step after the first: topology tables, constants (the coin among them) and the design (the
+      // previous step's result) are in LDS, this step's actions were parked there by rollout_stash -- nothing to fetch
       band_clear(T);
       return;
     }
@@ -396,6 +407,9 @@ struct StepLane {
       else if (T.blob_bytes <= BIT * 64 * 16) stage_fast<BIT>(T, A, decode);
       else stage_fast<BIT_BIG>(T, A, decode);
     } else {
+      const bool coin = coin_used(T, A);
+      int cb = 0;
+      if (coin) cb = A.coin[envc];   // issued first, stored last: no wait of its own
       {
         const tb_u4 *s4 = (const tb_u4 *)T.blob;
         tb_u4 *d4 = (tb_u4 *)TB;
@@ -411,6 +425,7 @@ struct StepLane {
         stage_row_slow(A.a_topo + bn * 3, tac(T), 3 * T.N);
       }
       band_clear(T);
+      if (coin) *coinsh(T) = cb;
     }
   }
 
@@ -455,6 +470,7 @@ struct StepLane {
   struct PairIn {
     int n0, n1, f0, f1;
     float y0, y1, ga0, ga1, gb0, gb1, ta[3], tb[3];
+    float mu0, md0, mu1, md1;   // the caller's move ranges (pair_ranges_load; only with A.mu_in)
   };
   TRUSS_HD void pair_load(const TopoDev &T, int p, PairIn &q) {
     const float *Y = ysh(T), *GE = geosh(T), *TA = tac(T);
@@ -475,6 +491,16 @@ struct StepLane {
       q.ta[j] = TA[3 * q.n0 + j];
       q.tb[j] = TA[3 * q.n1 + j];
     }
+  }
+  // move ranges passed in by the caller: they stay in HBM (the EMIT kernel has no LDS left for two more rows), at indices
+  // that come from the pair table -- so the loads of ALL of a lane's unrolled pairs are issued here, before pair_decode
+  // consumes the first (the pair index is clamped, the nodes are valid: no guard)
+  TRUSS_HD void pair_ranges_load(const TopoDev &T, const StepArgsDev &A, PairIn &q) const {
+    const size_t bn = (size_t)envc * T.N;
+    q.mu0 = A.mu_in[bn + q.n0];
+    q.md0 = A.md_in[bn + q.n0];
+    q.mu1 = A.mu_in[bn + q.n1];
+    q.md1 = A.md_in[bn + q.n1];
   }
   TRUSS_HD void pair_decode(const TopoDev &T, const StepArgsDev &A, PairIn &q, bool real) {
     const size_t bn = (size_t)envc * T.N;
@@ -501,11 +527,11 @@ struct StepLane {
       }
     }
     float mu0, md0, mu1, md1;
-    if (A.mu_in) {   // wave-uniform pointer test
-      mu0 = A.mu_in[bn + n0];
-      md0 = A.md_in[bn + n0];
-      mu1 = A.mu_in[bn + n1];
-      md1 = A.md_in[bn + n1];
+    if (A.mu_in) {   // wave-uniform pointer test; loaded by pair_ranges_load
+      mu0 = q.mu0;
+      md0 = q.md0;
+      mu1 = q.mu1;
+      md1 = q.md1;
     } else {
       move_range(top0, q.y0, q.y1, mu0, md0);
       move_range(top1, q.y1, q.y0, mu1, md1);
@@ -546,11 +572,16 @@ struct StepLane {
       const int p = g + G * i;
       pair_load(T, p < T.NP ? p : T.NP - 1, q[i]);
     }
+    if (A.mu_in) {   // wave-uniform
+#pragma unroll
+      for (int i = 0; i < PPL; ++i) pair_ranges_load(T, A, q[i]);
+    }
 #pragma unroll
     for (int i = 0; i < PPL; ++i) pair_decode(T, A, q[i], g + G * i < T.NP);
     for (int p = g + G * PPL; p < T.NP; p += G) {     // topologies with more pairs per lane than the unrolled part covers
       PairIn r;
       pair_load(T, p, r);
+      if (A.mu_in) pair_ranges_load(T, A, r);
       pair_decode(T, A, r, true);
     }
   }
@@ -559,6 +590,7 @@ struct StepLane {
   TRUSS_HD void phase_sym_nodes(const TopoDev &T) {
     float *Y = ysh(T);
     const int16_t *SN = t_symn(T);
+    const bool heads = *coinsh(T) != 0;   // parked by phase_stage (a launch without coin[] has no symmetric topology: truss_host.h)
     for (int i = g; i < T.n_sym_nodes; i += G) {
       int dst = SN[2 * i], src = SN[2 * i + 1];
       float v = heads ? Y[src] : Y[dst];
@@ -643,60 +675,88 @@ struct StepLane {
   }
 
   // ---- phase 4: element stiffness + scatter-add into the LDS band; load vector ----
+  // EBATCH: the LDS reads and the dependent float64 chains of all of a lane's elements are in flight together (phase_elements).
+  // Only where the register file has room for it: with two window rows per lane, a 16-wide window or 10 and more elements per
+  // lane the branch-free form cost AGPR copies on the pivot chain (and scratch in the 4-lane variant); those variants keep
+  // one element at a time behind the guard of its volume term, as before.
+  static constexpr bool EBATCH = RPL == 1 && W <= 8 && EPL <= 5;
+  static constexpr int ECH = EBATCH ? EPL : 1;
   TRUSS_HD void phase_elements(const TopoDev &T, const StepArgsDev &A) {
     const float *Y = ysh(T), *X = xsh(T);
     const int32_t *S = secsh(T);
     const int16_t *CN = t_conn(T);
     const double *AR = t_area(T), *ISR = t_isr(T);
     double *K = kb(T);
-    double kcc[EPL], kcs[EPL], kss[EPL];
-    // pass 1: gather + arithmetic for all of the lane's elements (no control flow: the square roots
-    // and divisions of different elements overlap)
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) {
-      const int e = g + G * i;
-      const int ee = e < T.E ? e : T.E - 1;
-      const int n0 = CN[2 * ee], n1 = CN[2 * ee + 1];
-      const int sc = S[ee];
-      const double dx = (double)X[n1] - (double)X[n0];
-      const double dy = (double)Y[n1] - (double)Y[n0];
-      const double l2 = dx * dx + dy * dy;
-      const double rl = tb_rsqrt(l2);  // 1/L: v_rsq_f64 seed + Newton (no f64 sqrt/div sequences)
-      const double len = l2 * rl;
-      const double c = dx * rl, s = dy * rl;
-      const double Aa = AR[sc];
-      const double k = (T.e_mod * Aa) * rl;
-      ek[i] = k;
-      ec[i] = c;
-      es[i] = s;
-      ei[i] = ISR[sc];
-      if constexpr (EMIT) el[i] = (float)len;   // nN_x_e column 2 (ENV:151)
-      if (e < T.E) p_vol += (double)(float)(Aa * len);  // all_v[i] is a float32 store (ENV:508)
-      const double kc = k * c, ks = k * s;
-      kcc[i] = kc * c;
-      kcs[i] = kc * s;
-      kss[i] = ks * s;
-    }
-    // pass 2 (FEM_2Dtruss.py:320-324 restricted to the lower band, without atomics): the four
-    // off-diagonal entries of an element belong to that element alone -> plain stores; the element's
-    // (k cc, k cs, k ss) go to LDS for the node-diagonal gather of phase_assemble_nodes.
     const int16_t *AC = t_asm(T);
     double *EV = evsh(T);
     if (g == 0) EV[3 * T.E] = EV[3 * T.E + 1] = EV[3 * T.E + 2] = 0.0;  // slot the padded adjacency points at
-    // branch-free: a lane index past the last element redoes element E-1 (same values to the same
-    // places), entries on restrained DOFs go to a trash slot behind the band
+    // Straight-line like phase_sizing, ECH elements at a time (all of them where EBATCH): their connectivity, sections and
+    // band offsets, then their coordinates and section constants, then the arithmetic and the stores -- the two LDS round
+    // trips are paid once and the chains of dependent float64 operations (v_rsq_f64, two Newton steps, ...) sit in one basic
+    // block.  No control flow: a guard around the volume term makes every element its own basic block, i.e. EPL times (two
+    // LDS round trips + one chain) in series.  A lane index past the last element redoes element E-1 (same values to the
+    // same places).
 #pragma unroll
-    for (int i = 0; i < EPL; ++i) {
-      const int e = g + G * i;
-      const int ee = e < T.E ? e : T.E - 1;
-      EV[3 * ee + 0] = kcc[i];
-      EV[3 * ee + 1] = kcs[i];
-      EV[3 * ee + 2] = kss[i];
-      const int16_t *code = AC + ee * 4;
-      K[code[0]] = -kcc[i];
-      K[code[1]] = -kss[i];
-      K[code[2]] = -kcs[i];
-      K[code[3]] = -kcs[i];
+    for (int c0 = 0; c0 < EPL; c0 += ECH) {
+      int n0[ECH], n1[ECH], sc[ECH], ev[ECH];
+      tb_u2 code[ECH];
+      float x0[ECH], x1[ECH], y0[ECH], y1[ECH];
+      double Aa[ECH];
+#pragma unroll
+      for (int j = 0; j < ECH; ++j) {
+        const int i = c0 + j < EPL ? c0 + j : EPL - 1;
+        const int e = g + G * i;
+        const int ee = e < T.E ? e : T.E - 1;
+        const uint32_t c = *(const uint32_t *)(CN + 2 * ee);    // both end nodes: one 4-byte read
+        n0[j] = (int)(int16_t)(c & 0xffffu);
+        n1[j] = (int)(int16_t)(c >> 16);
+        sc[j] = S[ee];
+        code[j] = *(const tb_u2 *)(AC + 4 * ee);                // the four band offsets: one 8-byte read
+        ev[j] = 3 * ee;
+      }
+#pragma unroll
+      for (int j = 0; j < ECH; ++j) {
+        x0[j] = X[n0[j]];
+        x1[j] = X[n1[j]];
+        y0[j] = Y[n0[j]];
+        y1[j] = Y[n1[j]];
+        Aa[j] = AR[sc[j]];
+      }
+      // FEM_2Dtruss.py:320-324 restricted to the lower band, without atomics: the four off-diagonal entries of an element
+      // belong to that element alone -> plain stores (entries on restrained DOFs go to a trash slot behind the band); the
+      // element's (k cc, k cs, k ss) go to LDS for the node-diagonal gather of phase_assemble_nodes.
+#pragma unroll
+      for (int j = 0; j < ECH; ++j) {
+        const int i = c0 + j;
+        if (i < EPL) {     // compile-time
+          const double dx = (double)x1[j] - (double)x0[j];
+          const double dy = (double)y1[j] - (double)y0[j];
+          const double l2 = dx * dx + dy * dy;
+          const double rl = tb_rsqrt(l2);  // 1/L: v_rsq_f64 seed + Newton (no f64 sqrt/div sequences)
+          const double len = l2 * rl;
+          const double c = dx * rl, s = dy * rl;
+          const double k = (T.e_mod * Aa[j]) * rl;
+          ek[i] = k;
+          ec[i] = c;
+          es[i] = s;
+          ei[i] = ISR[sc[j]];     // only stashed for post_elements: nothing in this phase waits for it
+          if constexpr (EMIT) el[i] = (float)len;   // nN_x_e column 2 (ENV:151)
+          // all_v[i] is a float32 store (ENV:508).  A select, not a guard: a lane index past the last element adds +0.0 to a
+          // sum of non-negative terms that starts at +0.0, which leaves its bits as they are
+          const double vol = (double)(float)(Aa[j] * len);
+          if constexpr (EBATCH) p_vol += (g + G * i < T.E) ? vol : 0.0;
+          else if (g + G * i < T.E) p_vol += vol;
+          const double kc = k * c, ks = k * s;
+          const double kcc = kc * c, kcs = kc * s, kss = ks * s;
+          EV[ev[j] + 0] = kcc;
+          EV[ev[j] + 1] = kcs;
+          EV[ev[j] + 2] = kss;
+          K[(int16_t)(code[j][0] & 0xffffu)] = -kcc;
+          K[(int16_t)(code[j][0] >> 16)] = -kss;
+          K[(int16_t)(code[j][1] & 0xffffu)] = -kcs;
+          K[(int16_t)(code[j][1] >> 16)] = -kcs;
+        }
+      }
     }
   }
 

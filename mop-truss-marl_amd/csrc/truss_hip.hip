@@ -349,7 +349,12 @@ __global__ __launch_bounds__(64) void truss_rollout_kernel(const RolloutDev P_) 
     const TopoDev &T = P.T;
     const StepArgsDev &A = P.A;
     StepLane<G, WL, RPL, EPL, false> ln;   // per step: no lane state is carried from one step to the next except through LDS
-    ln.init(threadIdx.x, blockIdx.x, T, A, smem);
+    // The lane index goes the same way: the lane-derived indices and LDS addresses of a step (clamped element / node / pair
+    // numbers, row offsets, ...) are a VALU instruction or two each, but hoisted out of the step loop they held ~80 VGPRs for
+    // the whole launch, and the allocator parked what the solver needs in AGPRs instead (v_accvgpr_read on the pivot chain).
+    int lane_id = threadIdx.x;
+    asm volatile("" : "+v"(lane_id));
+    ln.init(lane_id, blockIdx.x, T, A, smem);
     const int nset = (s + 1) % P.n_sets;
     ln.rs_first_step = s;
     ln.rs_y_out = (s & 1) ? (float *)A.y_in : A.y_out;          // step s reads buffer s & 1, writes the other one
