@@ -5,6 +5,10 @@
 // needs between the first load and the last store stays in LDS/registers: the assembled band of K
 // (n_pad x W float64), its L*D factor (in place), the load vector and the solution.  HBM sees only
 // the algorithmic bytes of the step (DESIGN.md "bytes per env-step").
+//
+// This file holds the step, rollout and observation kernels and their launch glue only.  Every other kernel family has a
+// header of its own, included at the end: truss_gcn.h, truss_gcn_level.h, truss_gcn_level_bwd.h, truss_replay.h, truss_front.h
+// (Pareto front + hypervolume) and truss_gcn_aggregate.h.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -214,6 +218,23 @@ __device__ __forceinline__ void tb_obs_timeout(LN &ln, char *lds, int o_flag, in
   if (ln.g == 0 && ln.active && status) atomicOr(&status[ln.env], TRUSS_STATUS_OBS_TIMEOUT);
 }
 
+// Phase boundaries of the step and rollout kernels (TRUSS_STEP_SCHEDULE / TRUSS_STREAM_SEG* of truss_body.h).  A wave has the
+// LDS bytes it works on to itself: its LDS instructions execute in issue order, so a later ds_read sees an earlier ds_write of
+// any lane without waiting for it.  A wavefront-scope fence plus wave_barrier keeps the compiler from reordering across a phase
+// boundary and emits no s_waitcnt / s_barrier (a __syncthreads() here costs a full LDS round trip per pivot of the
+// factorisation).  EMIT_POINT differs per kernel and is defined there; truss_obs_kernel redefines PH / PH_NS for itself.
+#define TB_WAVE_SYNC()                                    \
+  do {                                                    \
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
+    __builtin_amdgcn_wave_barrier();                      \
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
+  } while (0)
+#define PH(call) \
+  ln.call;       \
+  TB_WAVE_SYNC()
+#define PH_NS(call) ln.call
+#define BAR() TB_WAVE_SYNC()
+
 template <int G, int WL, int RPL, int EPL, bool EMIT>
 __global__ __launch_bounds__(EMIT ? 128 : 64) void truss_step_kernel(const TopoDev T, const StepArgsDev A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -229,11 +250,6 @@ __global__ __launch_bounds__(EMIT ? 128 : 64) void truss_step_kernel(const TopoD
     }
     __syncthreads();   // the only workgroup barrier of the kernel: the progress word starts at 0
     if (threadIdx.x >= 64) {
-#define SPH(call) \
-  ln.call;        \
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-  __builtin_amdgcn_wave_barrier();                        \
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront")
 #ifdef TRUSS_STAMPS
 #define SST(i)                                                                                        \
   do {                                                                                                \
@@ -254,19 +270,19 @@ __global__ __launch_bounds__(EMIT ? 128 : 64) void truss_step_kernel(const TopoD
       bool ok = tb_await(smem, T.o_flag, 1);
       if (ok) {
         SST(20);
-        TRUSS_STREAM_SEG1(SPH, T, A)
+        TRUSS_STREAM_SEG1(PH, T, A)
         SST(21);
         ok = tb_await(smem, T.o_flag, 2);
       }
       if (ok) {
         SST(22);
-        TRUSS_STREAM_SEG2(SPH, T, A)
+        TRUSS_STREAM_SEG2(PH, T, A)
         SST(23);
         ok = tb_await(smem, T.o_flag, 3);
       }
       if (ok) {
         SST(24);
-        TRUSS_STREAM_SEG3(SPH, T, A)
+        TRUSS_STREAM_SEG3(PH, T, A)
         SST(25);
       } else {
         tb_obs_timeout(ln, smem, T.o_flag, A.status);   // one exit for the three waits
@@ -276,36 +292,16 @@ __global__ __launch_bounds__(EMIT ? 128 : 64) void truss_step_kernel(const TopoD
       SST(26);
 #endif
 #undef SST
-#undef SPH
       return;
     }
   }
-  // The compute wave has the env's LDS bytes to itself: its LDS instructions execute in issue order, so a later
-  // ds_read sees an earlier ds_write of any lane without waiting for it.  A wavefront-scope fence plus
-  // wave_barrier keeps the compiler from reordering across a phase boundary and emits no s_waitcnt /
-  // s_barrier (a __syncthreads() here costs a full LDS round trip per pivot of the factorisation).
-#define TB_WAVE_SYNC()                                    \
-  do {                                                    \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-    __builtin_amdgcn_wave_barrier();                      \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-  } while (0)
-#define PH(call) \
-  ln.call;       \
-  TB_WAVE_SYNC()
-#define PH_NS(call) ln.call
-#define BAR() TB_WAVE_SYNC()
 #ifdef TRUSS_FAULT_DROP_PUBLISH3   // fault-injection build (make faultinj; tests only): progress 3 is never announced
 #define EMIT_POINT(k) do { if ((k) != 3) tb_publish(smem, T.o_flag, k); } while (0)
 #else
 #define EMIT_POINT(k) tb_publish(smem, T.o_flag, k)
 #endif
   TRUSS_STEP_SCHEDULE(PH, PH_NS, BAR, T, A)
-#undef PH
-#undef PH_NS
-#undef BAR
 #undef EMIT_POINT
-#undef TB_WAVE_SYNC
 }
 
 // truss_rollout as ONE launch: every workgroup plays its envs through all n_steps chained steps.  Topology tables,
@@ -324,17 +320,6 @@ __global__ __launch_bounds__(64) void truss_rollout_kernel(const RolloutDev P_) 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int W_ = StepLane<G, WL, RPL, EPL, false>::W;
   constexpr bool EMIT_ = false;
-#define TB_WAVE_SYNC()                                    \
-  do {                                                    \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-    __builtin_amdgcn_wave_barrier();                      \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-  } while (0)
-#define PH(call) \
-  ln.call;       \
-  TB_WAVE_SYNC()
-#define PH_NS(call) ln.call
-#define BAR() TB_WAVE_SYNC()
 #define EMIT_POINT(k) (void)0
   const int n_steps = P_.n_steps;
   for (int s = 0; s < n_steps; ++s) {
@@ -364,12 +349,13 @@ __global__ __launch_bounds__(64) void truss_rollout_kernel(const RolloutDev P_) 
     TRUSS_STEP_SCHEDULE(PH, PH_NS, BAR, T, A)
     TB_WAVE_SYNC();
   }
-#undef PH
+#undef EMIT_POINT
+}
+
+#undef PH   // the observation kernel's phases end in workgroup barriers
 #undef PH_NS
 #undef BAR
-#undef EMIT_POINT
 #undef TB_WAVE_SYNC
-}
 
 __global__ __launch_bounds__(64) void truss_obs_kernel(const TopoDev T, const ObsArgsDev A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -383,303 +369,6 @@ __global__ __launch_bounds__(64) void truss_obs_kernel(const TopoDev T, const Ob
   TRUSS_OBS_SCHEDULE(PH, PH_NS, T, A, r0_tile)
 #undef PH
 #undef PH_NS
-}
-
-// ---- batched Pareto front + hypervolume (truss_front) ------------------------------------------------
-// One 64-lane wave per env, lane i <-> input row i (P <= 64 rows of [obj1, obj2, con1, con2]).  Everything
-// quadratic in P is a loop over LDS broadcast reads; the order-sensitive float64 sums (distances, area)
-// are accumulated by lane 0 in index order, like the Python loops they replace.
-__global__ __launch_bounds__(64) void truss_front_kernel(const truss_front_args_t A) {
-  __shared__ double px[64], py[64], pc1[64], pc2[64];      // input rows
-  __shared__ double sx[64], sy[64], sd[64], scr[64];        // front sorted by obj1; distances; crowding
-  __shared__ int sidx[64], keep[64];
-  __shared__ double ax[64], ay[64];                         // all rows sorted by clipped x (hv_all)
-  const int b = blockIdx.x, i = threadIdx.x, P = A.max_points;
-  int n = A.n_points[b];
-  n = n < 0 ? 0 : (n > P ? P : n);
-  const bool have = i < n;
-  const double *row = A.points + ((size_t)b * P + (have ? i : 0)) * 4;
-  const double x = row[0], y = row[1], c1 = row[2], c2 = row[3];
-  px[i] = x; py[i] = y; pc1[i] = c1; pc2[i] = c2;
-  __syncthreads();
-  const bool feas = have && !(c1 > 1.0 || c2 > 1.0);
-  bool dom = false, dup = false;
-  for (int j = 0; j < n; ++j) {
-    const bool fj = !(pc1[j] > 1.0 || pc2[j] > 1.0);
-    dom |= fj && px[j] < x && py[j] < y;
-    dup |= fj && j < i && px[j] == x && py[j] == y && pc1[j] == c1 && pc2[j] == c2;
-  }
-  const bool fr = feas && !dom && !dup;
-  // position in the front sorted by (obj1, obj2, input order); the same for all rows by clipped x
-  const double cx = fmin(x, 1.0), cy = fmin(y, 1.0);
-  keep[i] = fr ? 1 : 0;
-  __syncthreads();
-  int rank = 0, arank = 0;
-  for (int j = 0; j < n; ++j) {
-    rank += keep[j] && (px[j] < x || (px[j] == x && (py[j] < y || (py[j] == y && j < i))));
-    const double cxj = fmin(px[j], 1.0);
-    arank += (cxj < cx || (cxj == cx && j < i));
-  }
-  __syncthreads();
-  const unsigned long long fmask = __ballot(fr);
-  int nf = __popcll(fmask);
-  if (fr) { sx[rank] = x; sy[rank] = y; sidx[rank] = i; }
-  if (have) { ax[arank] = cx; ay[arank] = cy; }
-  __syncthreads();
-  // crowding distance on the sorted front (utils.py:96-110)
-  if (i + 1 < nf) {
-    const double dx = sx[i] - sx[i + 1], dy = sy[i] - sy[i + 1];
-    sd[i] = sqrt(dx * dx + dy * dy);
-  }
-  __syncthreads();
-  if (i < nf) scr[i] = nf == 1 ? 0.0 : (i == 0 ? sd[0] : (i == nf - 1 ? sd[nf - 2] : sd[i - 1] + sd[i]));
-  __syncthreads();
-  // truncation to max_front (train copy): both ends + the interior points of largest crowding distance
-  bool kp = i < nf;
-  if ((A.flags & TRUSS_FRONT_TRUNCATE) && nf > A.max_front) {
-    if (i > 0 && i < nf - 1) {
-      int cr = 0;
-      for (int j = 1; j < nf - 1; ++j) cr += (scr[j] > scr[i] || (scr[j] == scr[i] && j < i));
-      kp = cr < A.max_front - 2;
-    }
-  }
-  const unsigned long long kmask = __ballot(kp);
-  const int pos = __popcll(kmask & ((1ull << i) - 1ull));
-  const int nk = __popcll(kmask);
-  const double kx = i < nf ? sx[i] : 0.0, ky = i < nf ? sy[i] : 0.0;
-  const int kid = i < nf ? sidx[i] : -1;
-  __syncthreads();
-  if (kp) { sx[pos] = kx; sy[pos] = ky; keep[pos] = kid; }
-  nf = nk;
-  __syncthreads();
-  if (i + 1 < nf) {
-    const double dx = sx[i] - sx[i + 1], dy = sy[i] - sy[i + 1];
-    sd[i] = sqrt(dx * dx + dy * dy);
-  }
-  if (A.front_idx && i < P) A.front_idx[(size_t)b * P + i] = i < nf ? keep[i] : -1;
-  __syncthreads();
-  if (i != 0) return;
-  if (A.n_front) A.n_front[b] = nf;
-  const double rx = A.ref_points ? A.ref_points[2 * b] : 1.0, ry = A.ref_points ? A.ref_points[2 * b + 1] : 1.0;
-  if (A.metrics) {
-    double maxd = 0.0, disd = 1.0, sumd = 0.0, stdcd = 1.0, pn = 0.0;
-    if (nf >= 2) {
-      maxd = sd[0];
-      for (int k = 0; k < nf - 1; ++k) { maxd = sd[k] > maxd ? sd[k] : maxd; sumd += sd[k]; }
-      double acc = 0.0;
-      const double ctr = maxd / (nf - 1);            // sic: the reference centres on max/len (utils.py:131)
-      for (int k = 0; k < nf - 1; ++k) acc += (sd[k] - ctr) * (sd[k] - ctr);
-      disd = sqrt(acc / (nf - 1));
-    }
-    if (nf > 3) {
-      double s = 0.0, mx = 0.0;
-      for (int k = 1; k < nf - 1; ++k) {
-        const double cd = fabs(sx[k - 1] - sx[k + 1]) + fabs(sy[k - 1] - sy[k + 1]);
-        scr[k] = cd; s += cd; mx = cd > mx ? cd : mx;
-      }
-      if (s != 0.0) {
-        const int m = nf - 2;
-        double mean = 0.0;
-        for (int k = 1; k < nf - 1; ++k) { scr[k] = scr[k] / mx; mean += scr[k]; }
-        mean /= m;
-        double var = 0.0, p10 = 0.0;
-        for (int k = 1; k < nf - 1; ++k) {
-          const double v = scr[k], d = v - mean;
-          var += d * d;
-          const double v2 = v * v, v4 = v2 * v2;
-          p10 += v4 * v4 * v2;
-        }
-        stdcd = sqrt(var / m);
-        pn = pow(p10, 0.1);
-      }
-    }
-    double *M = A.metrics + (size_t)b * 5;
-    M[0] = maxd; M[1] = disd; M[2] = pn; M[3] = sumd; M[4] = stdcd;
-  }
-  if (A.hv_front) {      // the front is sorted by obj1 and its obj2 decreases: closed form of the union area
-    double hv = 0.0;
-    if (nf > 0 && !(nf == 1 && sx[0] == 1.0 && sy[0] == 1.0)) {
-      double area = 0.0, runmin = 1.0, minx = sx[0], miny = sy[0];
-      for (int k = 0; k < nf; ++k) {
-        const double cxk = fmin(sx[k], 1.0), cyk = fmin(sy[k], 1.0);
-        runmin = cyk < runmin ? cyk : runmin;
-        const double nx = k + 1 < nf ? fmin(sx[k + 1], 1.0) : 1.0;
-        area += (nx - cxk) * (1.0 - runmin);
-        minx = sx[k] < minx ? sx[k] : minx;
-        miny = sy[k] < miny ? sy[k] : miny;
-      }
-      hv = area - ((1.0 - rx) * (1.0 - minx) + (1.0 - ry) * (1.0 - miny) - (1.0 - rx) * (1.0 - ry));
-    }
-    A.hv_front[b] = hv;
-  }
-  if (A.hv_all) {
-    double hv = 0.0;
-    if (n > 0 && !(n == 1 && px[0] == 1.0 && py[0] == 1.0)) {
-      double area = 0.0, runmin = 1.0, minx = px[0], miny = py[0];
-      for (int k = 0; k < n; ++k) {
-        runmin = ay[k] < runmin ? ay[k] : runmin;
-        const double nx = k + 1 < n ? ax[k + 1] : 1.0;
-        area += (nx - ax[k]) * (1.0 - runmin);
-        minx = px[k] < minx ? px[k] : minx;
-        miny = py[k] < miny ? py[k] : miny;
-      }
-      hv = area - ((1.0 - rx) * (1.0 - minx) + (1.0 - ry) * (1.0 - miny) - (1.0 - rx) * (1.0 - ry));
-    }
-    A.hv_all[b] = hv;
-  }
-}
-
-// ---- the same for 65..256 rows (truss_front_wide_kernel) ----------------------------------------------
-// One 256-thread workgroup (four wave64s) per env, thread i <-> input row i.  Dominance, duplicates, ranks,
-// crowding and the truncation rule are the loops of truss_front_kernel; what differs is that a 64-bit ballot
-// covers one wave only, so the front's size and the compaction after truncation add per-wave popcounts and a
-// prefix across the four waves through LDS.  Thread 0 accumulates the float64 sums in index order, as above.
-__global__ __launch_bounds__(256) void truss_front_wide_kernel(const truss_front_args_t A) {
-  constexpr int W = 256;
-  __shared__ double px[W], py[W], pc1[W], pc2[W];           // input rows
-  __shared__ double sx[W], sy[W], sd[W], scr[W];            // front sorted by obj1; distances; crowding
-  __shared__ int sidx[W], keep[W];
-  __shared__ double ax[W], ay[W];                           // all rows sorted by clipped x (hv_all)
-  __shared__ int wcnt[2][W / 64];                           // per-wave popcounts: front rows, kept rows
-  const int b = blockIdx.x, i = threadIdx.x, P = A.max_points;
-  const int wave = i >> 6, lane = i & 63;
-  int n = A.n_points[b];
-  n = n < 0 ? 0 : (n > P ? P : n);
-  const bool have = i < n;
-  const double *row = A.points + ((size_t)b * P + (have ? i : 0)) * 4;
-  const double x = row[0], y = row[1], c1 = row[2], c2 = row[3];
-  px[i] = x; py[i] = y; pc1[i] = c1; pc2[i] = c2;
-  __syncthreads();
-  const bool feas = have && !(c1 > 1.0 || c2 > 1.0);
-  bool dom = false, dup = false;
-  for (int j = 0; j < n; ++j) {
-    const bool fj = !(pc1[j] > 1.0 || pc2[j] > 1.0);
-    dom |= fj && px[j] < x && py[j] < y;
-    dup |= fj && j < i && px[j] == x && py[j] == y && pc1[j] == c1 && pc2[j] == c2;
-  }
-  const bool fr = feas && !dom && !dup;
-  const double cx = fmin(x, 1.0), cy = fmin(y, 1.0);
-  keep[i] = fr ? 1 : 0;
-  const unsigned long long fmask = __ballot(fr);
-  if (lane == 0) wcnt[0][wave] = __popcll(fmask);
-  __syncthreads();
-  int rank = 0, arank = 0;
-  for (int j = 0; j < n; ++j) {
-    rank += keep[j] && (px[j] < x || (px[j] == x && (py[j] < y || (py[j] == y && j < i))));
-    const double cxj = fmin(px[j], 1.0);
-    arank += (cxj < cx || (cxj == cx && j < i));
-  }
-  int nf = 0;
-  for (int w = 0; w < W / 64; ++w) nf += wcnt[0][w];
-  __syncthreads();
-  if (fr) { sx[rank] = x; sy[rank] = y; sidx[rank] = i; }
-  if (have) { ax[arank] = cx; ay[arank] = cy; }
-  __syncthreads();
-  // crowding distance on the sorted front (utils.py:96-110)
-  if (i + 1 < nf) {
-    const double dx = sx[i] - sx[i + 1], dy = sy[i] - sy[i + 1];
-    sd[i] = sqrt(dx * dx + dy * dy);
-  }
-  __syncthreads();
-  if (i < nf) scr[i] = nf == 1 ? 0.0 : (i == 0 ? sd[0] : (i == nf - 1 ? sd[nf - 2] : sd[i - 1] + sd[i]));
-  __syncthreads();
-  // truncation to max_front: both ends + the interior points of largest crowding distance (ties: position)
-  bool kp = i < nf;
-  if ((A.flags & TRUSS_FRONT_TRUNCATE) && nf > A.max_front) {
-    if (i > 0 && i < nf - 1) {
-      int cr = 0;
-      for (int j = 1; j < nf - 1; ++j) cr += (scr[j] > scr[i] || (scr[j] == scr[i] && j < i));
-      kp = cr < A.max_front - 2;
-    }
-  }
-  const unsigned long long kmask = __ballot(kp);
-  if (lane == 0) wcnt[1][wave] = __popcll(kmask);
-  const double kx = i < nf ? sx[i] : 0.0, ky = i < nf ? sy[i] : 0.0;
-  const int kid = i < nf ? sidx[i] : -1;
-  __syncthreads();
-  int pos = __popcll(kmask & ((1ull << lane) - 1ull)), nk = 0;
-  for (int w = 0; w < W / 64; ++w) {
-    pos += w < wave ? wcnt[1][w] : 0;
-    nk += wcnt[1][w];
-  }
-  if (kp) { sx[pos] = kx; sy[pos] = ky; keep[pos] = kid; }
-  nf = nk;
-  __syncthreads();
-  if (i + 1 < nf) {
-    const double dx = sx[i] - sx[i + 1], dy = sy[i] - sy[i + 1];
-    sd[i] = sqrt(dx * dx + dy * dy);
-  }
-  if (A.front_idx && i < P) A.front_idx[(size_t)b * P + i] = i < nf ? keep[i] : -1;
-  __syncthreads();
-  if (i != 0) return;
-  if (A.n_front) A.n_front[b] = nf;
-  const double rx = A.ref_points ? A.ref_points[2 * b] : 1.0, ry = A.ref_points ? A.ref_points[2 * b + 1] : 1.0;
-  if (A.metrics) {
-    double maxd = 0.0, disd = 1.0, sumd = 0.0, stdcd = 1.0, pn = 0.0;
-    if (nf >= 2) {
-      maxd = sd[0];
-      for (int k = 0; k < nf - 1; ++k) { maxd = sd[k] > maxd ? sd[k] : maxd; sumd += sd[k]; }
-      double acc = 0.0;
-      const double ctr = maxd / (nf - 1);            // sic: the reference centres on max/len (utils.py:131)
-      for (int k = 0; k < nf - 1; ++k) acc += (sd[k] - ctr) * (sd[k] - ctr);
-      disd = sqrt(acc / (nf - 1));
-    }
-    if (nf > 3) {
-      double s = 0.0, mx = 0.0;
-      for (int k = 1; k < nf - 1; ++k) {
-        const double cd = fabs(sx[k - 1] - sx[k + 1]) + fabs(sy[k - 1] - sy[k + 1]);
-        scr[k] = cd; s += cd; mx = cd > mx ? cd : mx;
-      }
-      if (s != 0.0) {
-        const int m = nf - 2;
-        double mean = 0.0;
-        for (int k = 1; k < nf - 1; ++k) { scr[k] = scr[k] / mx; mean += scr[k]; }
-        mean /= m;
-        double var = 0.0, p10 = 0.0;
-        for (int k = 1; k < nf - 1; ++k) {
-          const double v = scr[k], d = v - mean;
-          var += d * d;
-          const double v2 = v * v, v4 = v2 * v2;
-          p10 += v4 * v4 * v2;
-        }
-        stdcd = sqrt(var / m);
-        pn = pow(p10, 0.1);
-      }
-    }
-    double *M = A.metrics + (size_t)b * 5;
-    M[0] = maxd; M[1] = disd; M[2] = pn; M[3] = sumd; M[4] = stdcd;
-  }
-  if (A.hv_front) {
-    double hv = 0.0;
-    if (nf > 0 && !(nf == 1 && sx[0] == 1.0 && sy[0] == 1.0)) {
-      double area = 0.0, runmin = 1.0, minx = sx[0], miny = sy[0];
-      for (int k = 0; k < nf; ++k) {
-        const double cxk = fmin(sx[k], 1.0), cyk = fmin(sy[k], 1.0);
-        runmin = cyk < runmin ? cyk : runmin;
-        const double nx = k + 1 < nf ? fmin(sx[k + 1], 1.0) : 1.0;
-        area += (nx - cxk) * (1.0 - runmin);
-        minx = sx[k] < minx ? sx[k] : minx;
-        miny = sy[k] < miny ? sy[k] : miny;
-      }
-      hv = area - ((1.0 - rx) * (1.0 - minx) + (1.0 - ry) * (1.0 - miny) - (1.0 - rx) * (1.0 - ry));
-    }
-    A.hv_front[b] = hv;
-  }
-  if (A.hv_all) {
-    double hv = 0.0;
-    if (n > 0 && !(n == 1 && px[0] == 1.0 && py[0] == 1.0)) {
-      double area = 0.0, runmin = 1.0, minx = px[0], miny = py[0];
-      for (int k = 0; k < n; ++k) {
-        runmin = ay[k] < runmin ? ay[k] : runmin;
-        const double nx = k + 1 < n ? ax[k + 1] : 1.0;
-        area += (nx - ax[k]) * (1.0 - runmin);
-        minx = px[k] < minx ? px[k] : minx;
-        miny = py[k] < miny ? py[k] : miny;
-      }
-      hv = area - ((1.0 - rx) * (1.0 - minx) + (1.0 - ry) * (1.0 - miny) - (1.0 - rx) * (1.0 - ry));
-    }
-    A.hv_all[b] = hv;
-  }
 }
 
 // ---- host backend ---------------------------------------------------------------------------
@@ -800,283 +489,4 @@ extern "C" int truss_debug_stamps(unsigned long long *out16) {
 #include "truss_replay.h"
 
 #include "truss_front.h"
-extern "C" int truss_front(const truss_front_args_t *a, void *stream) {
-  if (int rc = tb_front_check(a)) return rc;
-  if (a->n_envs == 0) return TRUSS_OK;
-  if (a->max_points <= 64)
-    hipLaunchKernelGGL(truss_front_kernel, dim3((unsigned)a->n_envs), dim3(64), 0, (hipStream_t)stream, *a);
-  else
-    hipLaunchKernelGGL(truss_front_wide_kernel, dim3((unsigned)a->n_envs), dim3(256), 0, (hipStream_t)stream, *a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("front kernel launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
-}
-
-// ---- GCN aggregation (inference): one workgroup per env and 256 channels, thread = channel -------------
-// Memory-bound (reads H once, writes out once, 16-64 FMAs per element): every global access is a contiguous
-// run of channels across the threads of a wave; the adjacency row block sits in LDS and is read as a
-// broadcast.  Bias and activation are fused (no extra passes over the [B, N, C] tensor).
-template <int NMAX>
-__global__ __launch_bounds__(256) void truss_gcn_aggregate_kernel(const float *__restrict__ adj, long a_stride, const float *h,
-                                                                  const float *__restrict__ bias, float *out, int N, int C, int act) {
-  __shared__ float sA[NMAX * NMAX];
-  const int b = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
-  const float *A = adj + (size_t)b * a_stride;
-  for (int i = threadIdx.x; i < N * N; i += 256) sA[i] = A[i];
-  __syncthreads();
-  if (c >= C) return;
-  const float *H = h + (size_t)b * N * C + c;
-  float col[NMAX];
-#pragma unroll
-  for (int j = 0; j < NMAX; ++j) col[j] = j < N ? H[(size_t)j * C] : 0.0f;
-  const float bc = bias ? bias[c] : 0.0f;
-  float *O = out + (size_t)b * N * C + c;
-  for (int i = 0; i < N; ++i) {
-    float acc = bc;
-#pragma unroll
-    for (int j = 0; j < NMAX; ++j) acc = fmaf(j < N ? sA[i * N + j] : 0.0f, col[j], acc);
-    if (act == 1) acc = acc > 0.0f ? acc : 0.0f;
-    else if (act == 2) acc = 1.0f / (1.0f + expf(-acc));
-    O[(size_t)i * C] = acc;
-  }
-}
-
-// The same for channel counts that are multiples of 4, sized to the channel count: a thread owns FOUR channels of one
-// graph (16-byte loads / stores) and the threads of a block are dealt over (graph, channel quad) pairs without gaps, so
-// no lane idles whatever C is (thread = channel in 256-wide blocks left 22 % of the lanes idle at C = 200); a block of
-// 256 threads then spans up to 256 / (C / 4) + 2 graphs, whose adjacencies it stages in LDS.
-template <int NMAX>
-__global__ __launch_bounds__(256) void truss_gcn_aggregate4_kernel(const float *__restrict__ adj, long a_stride, const float *h,
-                                                                   const float *__restrict__ bias, float *out, int B, int N, int C4, int act,
-                                                                   int gmax) {
-  extern __shared__ float sA[];                       // [graphs of this block][N][N]
-  const long t0 = (long)blockIdx.x * 256, t = t0 + threadIdx.x;
-  const int g0 = (int)(t0 / C4);
-  int g1 = (int)((t0 + 255) / C4);
-  g1 = g1 < B - 1 ? g1 : B - 1;
-  const int ng = a_stride ? g1 - g0 + 1 : 1, nn = N * N;
-  for (int i = threadIdx.x; i < ng * nn; i += 256) sA[i] = adj[(a_stride ? (size_t)(g0 + i / nn) * a_stride : 0) + i % nn];
-  __syncthreads();
-  const int gph = (int)(t / C4), c4 = (int)(t % C4);
-  if (gph >= B) return;
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const f4 *H = (const f4 *)h + ((size_t)gph * N) * C4 + c4;
-  f4 col[NMAX];
-#pragma unroll
-  for (int j = 0; j < NMAX; ++j) col[j] = j < N ? H[(size_t)j * C4] : (f4){0.0f, 0.0f, 0.0f, 0.0f};
-  const f4 bc = bias ? ((const f4 *)bias)[c4] : (f4){0.0f, 0.0f, 0.0f, 0.0f};
-  const float *A = sA + (a_stride ? (gph - g0) * nn : 0);
-  f4 *O = (f4 *)out + ((size_t)gph * N) * C4 + c4;
-  for (int i = 0; i < N; ++i) {
-    f4 acc = bc;
-#pragma unroll
-    for (int j = 0; j < NMAX; ++j) {
-      const float aij = j < N ? A[i * N + j] : 0.0f;
-      acc[0] = fmaf(aij, col[j][0], acc[0]);
-      acc[1] = fmaf(aij, col[j][1], acc[1]);
-      acc[2] = fmaf(aij, col[j][2], acc[2]);
-      acc[3] = fmaf(aij, col[j][3], acc[3]);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (act == 1) acc[q] = acc[q] > 0.0f ? acc[q] : 0.0f;
-      else if (act == 2) acc[q] = 1.0f / (1.0f + expf(-acc[q]));
-    }
-    O[(size_t)i * C4] = acc;
-  }
-}
-
-// Slab variant (dense or sparse pattern): a block owns a 128-byte channel slab (8 quads) of GB whole graphs.  It stages the slab of
-// H in LDS with full-line loads (8 threads = one 128-byte line), then every (graph, row, quad) item sums its terms from LDS and
-// stores 16 bytes -- 8 items = one whole line.  HBM sees H once and `out` once; the neighbours' rows come from LDS, not from L2.
-// nbr == nullptr: dense, the K = N columns in order.
-__global__ __launch_bounds__(256) void truss_gcn_aggregate_slab_kernel(const float *__restrict__ adj, long a_stride,
-                                                                       const int16_t *__restrict__ nbr, int K, const float *__restrict__ h,
-                                                                       const float *__restrict__ bias, float *__restrict__ out, int B, int N,
-                                                                       int C4, int GB, int act) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  extern __shared__ f4 sH[];                              // [GB][N][8]
-  const int slab = blockIdx.y, q0 = slab * 8;
-  const int nq = C4 - q0 < 8 ? C4 - q0 : 8;               // quads of this slab (the last one may be short)
-  const int b0 = blockIdx.x * GB;
-  const int gb = B - b0 < GB ? B - b0 : GB;
-  const int items = gb * N * 8;
-  for (int it = threadIdx.x; it < items; it += 256) {
-    const int q = it & 7, r = it >> 3;                    // r = g * N + row
-    if (q < nq) sH[it] = ((const f4 *)h)[((size_t)b0 * N + r) * C4 + q0 + q];
-  }
-  __syncthreads();
-  for (int it = threadIdx.x; it < items; it += 256) {
-    const int q = it & 7, r = it >> 3;
-    if (q >= nq) continue;
-    const int g = r / N, i = r - g * N;
-    const float *Arow = adj + (size_t)(b0 + g) * a_stride + (size_t)i * N;
-    const f4 *Hg = sH + (size_t)g * N * 8 + q;
-    f4 acc = bias ? ((const f4 *)bias)[q0 + q] : (f4){0.0f, 0.0f, 0.0f, 0.0f};
-    if (nbr) {
-      const int16_t *nb = nbr + (size_t)i * K;
-      for (int k = 0; k < K; ++k) {     // (an unrolled round of 12 with all loads in flight was slower: 45 against 34 us at 64 nodes)
-        const int j = nb[k];
-        if (j < 0) continue;
-        const float a = Arow[j];
-        const f4 hv = Hg[j * 8];
-        acc[0] = fmaf(a, hv[0], acc[0]);
-        acc[1] = fmaf(a, hv[1], acc[1]);
-        acc[2] = fmaf(a, hv[2], acc[2]);
-        acc[3] = fmaf(a, hv[3], acc[3]);
-      }
-    } else {
-      for (int j = 0; j < N; ++j) {
-        const float a = Arow[j];
-        const f4 hv = Hg[j * 8];
-        acc[0] = fmaf(a, hv[0], acc[0]);
-        acc[1] = fmaf(a, hv[1], acc[1]);
-        acc[2] = fmaf(a, hv[2], acc[2]);
-        acc[3] = fmaf(a, hv[3], acc[3]);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (act == 1) acc[c] = acc[c] > 0.0f ? acc[c] : 0.0f;
-      else if (act == 2) acc[c] = 1.0f / (1.0f + expf(-acc[c]));
-    }
-    ((f4 *)out)[((size_t)b0 * N + r) * C4 + q0 + q] = acc;
-  }
-}
-// launch helper: false when the shape does not suit the slab kernel (the callers' other kernels take over)
-static bool tb_launch_gcn_slab(const float *adj, int64_t a_stride, const int16_t *nbr, int K, const float *h, const float *bias, float *out,
-                               int B, int N, int C, int act, hipStream_t st) {
-  if ((C & 3) || (((size_t)h | (size_t)out | (size_t)bias) & 15) != 0) return false;   // (out may alias h: a block reads its whole tile first)
-  const int GB = std::max(1, tb_env_int("TRUSS_GCN_SLAB_ITEMS", 512) / (8 * N));   // graphs per block: >= two rounds of items for small graphs
-  const size_t lds = (size_t)GB * N * 8 * 16;
-  if (lds > 48 * 1024) return false;
-  const int C4 = C / 4;
-  dim3 grid((unsigned)((B + GB - 1) / GB), (unsigned)((C4 + 7) / 8));
-  hipLaunchKernelGGL(truss_gcn_aggregate_slab_kernel, grid, dim3(256), lds, st, adj, (long)a_stride, nbr, K, h, bias, out, B, N, C4, GB, act);
-  return true;
-}
-
-// Sparse-pattern variant: thread = (graph, row, channel quad), flat over the launch; a row's <= 16 listed neighbours instead of
-// all N columns.  The H rows a thread reads are 16-byte loads that the threads of a row issue contiguously (C floats); a graph's
-// rows are re-read by their neighbours' threads from L2 / L1, so HBM sees H once and `out` once.
-template <int KR>   // neighbours per round: all loads of a round are in flight together (KR = 12 covers a truss row in one round)
-__global__ __launch_bounds__(256) void truss_gcn_aggregate_sparse_kernel(const float *__restrict__ adj, long a_stride,
-                                                                         const int16_t *__restrict__ nbr, int K, const float *__restrict__ h,
-                                                                         const float *__restrict__ bias, float *__restrict__ out, long total,
-                                                                         int N, int C4, int act) {
-  const long t = (long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= total) return;
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const int c4 = (int)(t % C4);
-  const long r = t / C4;
-  const int i = (int)(r % N);
-  const long b = r / N;
-  const float *Arow = adj + b * a_stride + (long)i * N;
-  const f4 *Hb = (const f4 *)h + (size_t)b * N * C4 + c4;
-  const int16_t *nb = nbr + (long)i * K;
-  f4 acc = bias ? ((const f4 *)bias)[c4] : (f4){0.0f, 0.0f, 0.0f, 0.0f};
-  for (int k0 = 0; k0 < K; k0 += KR) {
-    int j[KR];
-    float a[KR];
-    f4 hv[KR];
-#pragma unroll
-    for (int q = 0; q < KR; ++q) {
-      j[q] = k0 + q < K ? (int)nb[k0 + q] : -1;
-      const int jc = j[q] < 0 ? i : j[q];
-      a[q] = Arow[jc];
-      hv[q] = Hb[(size_t)jc * C4];
-    }
-#pragma unroll
-    for (int q = 0; q < KR; ++q) {
-      if (j[q] < 0) continue;
-      acc[0] = fmaf(a[q], hv[q][0], acc[0]);
-      acc[1] = fmaf(a[q], hv[q][1], acc[1]);
-      acc[2] = fmaf(a[q], hv[q][2], acc[2]);
-      acc[3] = fmaf(a[q], hv[q][3], acc[3]);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (act == 1) acc[q] = acc[q] > 0.0f ? acc[q] : 0.0f;
-    else if (act == 2) acc[q] = 1.0f / (1.0f + expf(-acc[q]));
-  }
-  ((f4 *)out)[t] = acc;
-}
-
-extern "C" int truss_gcn_aggregate_sparse(const float *adj, int64_t a_batch_stride, const int16_t *nbr, int32_t k_nbr, const float *h,
-                                          const float *bias, float *out, int32_t n_batch, int32_t n_nodes, int32_t n_channels,
-                                          int32_t act, void *stream) {
-  if (!adj || !nbr || !h || !out) return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate_sparse: NULL argument");
-  if (n_batch < 0 || n_nodes < 1 || n_nodes > 32767 || k_nbr < 1 || k_nbr > 16 || n_channels < 4 || (n_channels & 3) || act < 0 || act > 2)
-    return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate_sparse: n_nodes 1..32767, k_nbr 1..16, n_channels a multiple of 4, act 0..2");
-  if ((((size_t)h | (size_t)out | (size_t)bias) & 15) != 0 || h == out)
-    return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate_sparse: h / out / bias must be 16-byte aligned, out must not alias h");
-  if (n_batch == 0) return TRUSS_OK;
-  // up to 128 nodes the slab kernel (rows from LDS: 33-36 us at 64 / 128 nodes against 40-42; at 256 nodes a block walks 8 rounds
-  // over its 32 KB tile and loses: 52 against 42 us, tools/agg_probe.py)
-  if (n_nodes <= tb_env_int("TRUSS_GCN_SLAB_MAX_N", 128) &&
-      tb_launch_gcn_slab(adj, a_batch_stride, nbr, k_nbr, h, bias, out, n_batch, n_nodes, n_channels, act, (hipStream_t)stream)) {
-    hipError_t es = hipGetLastError();
-    if (es != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn slab aggregate launch failed: ") + hipGetErrorString(es));
-    return TRUSS_OK;
-  }
-  const int C4 = n_channels / 4;
-  const long total = (long)n_batch * n_nodes * C4;
-  const dim3 grid((unsigned)((total + 255) / 256));
-  if (k_nbr <= 4)
-    hipLaunchKernelGGL(truss_gcn_aggregate_sparse_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, adj, (long)a_batch_stride, nbr, k_nbr, h,
-                       bias, out, total, n_nodes, C4, act);
-  else if (k_nbr <= 8)
-    hipLaunchKernelGGL(truss_gcn_aggregate_sparse_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, adj, (long)a_batch_stride, nbr, k_nbr, h,
-                       bias, out, total, n_nodes, C4, act);
-  else
-    hipLaunchKernelGGL(truss_gcn_aggregate_sparse_kernel<12>, grid, dim3(256), 0, (hipStream_t)stream, adj, (long)a_batch_stride, nbr, k_nbr, h,
-                       bias, out, total, n_nodes, C4, act);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn sparse aggregate launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
-}
-
-extern "C" int truss_gcn_aggregate(const float *adj, int64_t a_batch_stride, const float *h, const float *bias, float *out,
-                                   int32_t n_batch, int32_t n_nodes, int32_t n_channels, int32_t act, void *stream) {
-  if (!adj || !h || !out) return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate: NULL argument");
-  if (n_batch < 0 || n_nodes < 1 || n_nodes > 64 || n_channels < 1 || act < 0 || act > 2)
-    return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate: n_nodes must be 1..64, act 0..2");
-  if (n_batch == 0) return TRUSS_OK;
-  // 17..64 nodes: the slab kernel (32 nodes: 58-61 us against 73-84 for the channel-quad kernel below, 64 nodes: 44 against 182 for
-  // the thread-per-channel kernel and 75 for rocBLAS + bias + activation); <= 16 nodes: the channel-quad kernel (56 against 74 us)
-  if (n_nodes > tb_env_int("TRUSS_GCN_SLAB_DENSE_ABOVE", 16) && tb_launch_gcn_slab(adj, a_batch_stride, nullptr, n_nodes, h, bias, out, n_batch, n_nodes, n_channels, act, (hipStream_t)stream)) {
-    hipError_t es = hipGetLastError();
-    if (es != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn slab aggregate launch failed: ") + hipGetErrorString(es));
-    return TRUSS_OK;
-  }
-  if ((n_channels & 3) == 0 && n_nodes <= 32 && (((size_t)h | (size_t)out | (size_t)bias) & 15) == 0) {
-    // channel-quad threads, no idle lanes
-    const int C4 = n_channels / 4;
-    const int gmax = a_batch_stride ? 256 / C4 + 2 : 1;
-    const size_t lds = (size_t)gmax * n_nodes * n_nodes * sizeof(float);
-    const long total = (long)n_batch * C4;
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (lds <= 64 * 1024) {
-      if (n_nodes <= 16)
-        hipLaunchKernelGGL(truss_gcn_aggregate4_kernel<16>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, adj, (long)a_batch_stride, h, bias, out,
-                           n_batch, n_nodes, C4, act, gmax);
-      else
-        hipLaunchKernelGGL(truss_gcn_aggregate4_kernel<32>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, adj, (long)a_batch_stride, h, bias, out,
-                           n_batch, n_nodes, C4, act, gmax);
-      hipError_t e4 = hipGetLastError();
-      if (e4 != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn aggregate launch failed: ") + hipGetErrorString(e4));
-      return TRUSS_OK;
-    }
-  }
-  dim3 grid((unsigned)n_batch, (unsigned)((n_channels + 255) / 256));
-  if (n_nodes <= 16)
-    hipLaunchKernelGGL(truss_gcn_aggregate_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, adj, (long)a_batch_stride, h, bias, out, n_nodes, n_channels, act);
-  else if (n_nodes <= 32)
-    hipLaunchKernelGGL(truss_gcn_aggregate_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, adj, (long)a_batch_stride, h, bias, out, n_nodes, n_channels, act);
-  else
-    hipLaunchKernelGGL(truss_gcn_aggregate_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, adj, (long)a_batch_stride, h, bias, out, n_nodes, n_channels, act);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn aggregate launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
-}
+#include "truss_gcn_aggregate.h"

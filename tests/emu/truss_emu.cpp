@@ -222,7 +222,7 @@ static int tb_launch_obs(const truss_topo *t, const ObsArgsDev &A, void *) {
   return TRUSS_OK;
 }
 
-// ---- truss_front: serial restatement for the CPU test backend (the HIP kernel is in truss_hip.hip) ----
+// ---- truss_front: serial restatement for the CPU test backend (the HIP kernel is in truss_front.h, below the shared argument check) ----
 #include "../../mop-truss-marl_amd/csrc/truss_front.h"
 #include <cmath>
 #include <vector>
@@ -348,14 +348,12 @@ extern "C" int truss_front(const truss_front_args_t *a, void *) {
   return TRUSS_OK;
 }
 
+// ---- truss_gcn_aggregate / _sparse: plain loops behind the argument checks the HIP entries use ----
+#include "../../mop-truss-marl_amd/csrc/truss_gcn_aggregate.h"
 extern "C" int truss_gcn_aggregate_sparse(const float *adj, int64_t a_batch_stride, const int16_t *nbr, int32_t k_nbr, const float *h,
                                           const float *bias, float *out, int32_t n_batch, int32_t n_nodes, int32_t n_channels,
                                           int32_t act, void *) {
-  if (!adj || !nbr || !h || !out) return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate_sparse: NULL argument");
-  if (n_batch < 0 || n_nodes < 1 || n_nodes > 32767 || k_nbr < 1 || k_nbr > 16 || n_channels < 4 || (n_channels & 3) || act < 0 || act > 2)
-    return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate_sparse: n_nodes 1..32767, k_nbr 1..16, n_channels a multiple of 4, act 0..2");
-  if ((((size_t)h | (size_t)out | (size_t)bias) & 15) != 0 || h == out)
-    return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate_sparse: h / out / bias must be 16-byte aligned, out must not alias h");
+  if (int rc = tb_gcn_aggregate_sparse_check(adj, nbr, k_nbr, h, bias, out, n_batch, n_nodes, n_channels, act)) return rc;
   const int N = n_nodes, C = n_channels;
   for (int b = 0; b < n_batch; ++b) {
     const float *A = adj + (size_t)b * a_batch_stride, *H = h + (size_t)b * N * C;
@@ -376,9 +374,7 @@ extern "C" int truss_gcn_aggregate_sparse(const float *adj, int64_t a_batch_stri
 
 extern "C" int truss_gcn_aggregate(const float *adj, int64_t a_batch_stride, const float *h, const float *bias, float *out,
                                    int32_t n_batch, int32_t n_nodes, int32_t n_channels, int32_t act, void *) {
-  if (!adj || !h || !out) return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate: NULL argument");
-  if (n_batch < 0 || n_nodes < 1 || n_nodes > 64 || n_channels < 1 || act < 0 || act > 2)
-    return tb_fail(TRUSS_EINVAL, "truss_gcn_aggregate: n_nodes must be 1..64, act 0..2");
+  if (int rc = tb_gcn_aggregate_check(adj, h, out, n_batch, n_nodes, n_channels, act)) return rc;
   const int N = n_nodes, C = n_channels;
   std::vector<float> tmp((size_t)N * C);
   for (int b = 0; b < n_batch; ++b) {

@@ -1,7 +1,7 @@
 """`truss_front` above 64 rows (the 256-thread kernel, include/truss_mi355.h): ragged batches of up to 256 rows per env
 against the drop-in utils.simple_cull_final / union_rectangles_fastest, the D3 truncation against a Python restatement,
 and the HIP kernel against the serial CPU restatement (tests/emu) on the same inputs.  Sets of at most 64 rows in the same
-batch shapes go through the 64-row kernel (max_points <= 64) and must give the same results as before."""
+batch shapes go through the 64-thread instance of the same kernel (max_points <= 64) and must give the same results as before."""
 import math
 
 import numpy as np
@@ -48,7 +48,7 @@ def _run(lib, device, pts, n, ref, max_front):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def _check_reference(out, pts, n, ref):
+def _check_reference(out, pts, n, ref, min_long=4):
     """no truncation: front set and order, n_front, metrics and both HVs against the drop-in utils"""
     long_fronts = 0
     for b in range(len(n)):
@@ -69,7 +69,7 @@ def _check_reference(out, pts, n, ref):
         hva = U.union_rectangles_fastest(rows, +1, -1, ref_point=list(ref[b]))
         assert abs(out["hv_front"][b] - hv) <= 1e-12 and abs(out["hv_all"][b] - hva) <= 1e-12, b
         long_fronts += nf > 64
-    assert long_fronts >= 4                                              # the cases exercise fronts longer than one wave
+    assert long_fronts >= min_long                                       # the cases exercise fronts longer than one wave
 
 
 def _d3(pts_b, full_idx, max_front):
@@ -105,17 +105,29 @@ def _same(a, b, what):
         np.testing.assert_allclose(a[k], b[k], rtol=0, atol=1e-12, err_msg=f"{what}: {k}")
 
 
-def _check(lib, device, seed):
-    pts, n, ref = _sets(seed)
+def _check(lib, device, seed, P=256, min_long=4, max_fronts=(20, 50)):
+    pts, n, ref = _sets(seed, P)
     full = _run(lib, device, pts, n, ref, 0)
-    _check_reference(full, pts, n, ref)
-    for mf in (20, 50):
+    _check_reference(full, pts, n, ref, min_long)
+    for mf in max_fronts:
         _check_truncation(_run(lib, device, pts, n, ref, mf), full, pts, n, mf)
     return pts, n, ref, full
 
 
+# max_points strictly between 64 and 256: the 256-thread kernel with fewer rows than threads.  200 rows is what the design game
+# culls; 65 rows put one row into the second wave, the smallest shape at which the prefix across waves can go wrong -- there
+# _sets() makes no front longer than 64 (so no long-front cap) and only one or two longer than 50 (so truncation to 20 only).
+BETWEEN = {200: dict(P=200), 65: dict(P=65, min_long=0, max_fronts=(20,))}
+
+
 def test_front_wide_emulated():
     _check(pc.emu_lib(), "cpu", 5)
+
+
+@pytest.mark.parametrize("P", sorted(BETWEEN))
+@pytest.mark.parametrize("seed", [5, 6])
+def test_front_between_emulated(seed, P):
+    _check(pc.emu_lib(), "cpu", seed, **BETWEEN[P])
 
 
 def test_front_limits_emulated():
@@ -127,19 +139,30 @@ def test_front_limits_emulated():
     assert out["n_front"].tolist() == [0, 1] and out["hv_front"].tolist() == [0.0, 1.0]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("seed", [5, 6])
-def test_front_wide_hip(seed):
-    pts, n, ref, full = _check(tm.load(), "cuda", seed)
+def _check_hip(seed, **shape):
+    pts, n, ref, full = _check(tm.load(), "cuda", seed, **shape)
     emu = pc.emu_lib()
     _same(full, _run(emu, "cpu", pts, n, ref, 0), "no truncation")
-    for mf in (20, 50):
+    for mf in shape.get("max_fronts", (20, 50)):
         _same(_run(tm.load(), "cuda", pts, n, ref, mf), _run(emu, "cpu", pts, n, ref, mf), f"max_front {mf}")
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("seed", [5, 6])
+def test_front_wide_hip(seed):
+    _check_hip(seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", sorted(BETWEEN))
+@pytest.mark.parametrize("seed", [5, 6])
+def test_front_between_hip(seed, P):
+    _check_hip(seed, **BETWEEN[P])
+
+
+@pytest.mark.gpu
 def test_front_narrow_unchanged_hip():
-    """at most 64 rows: the 64-row kernel, bitwise the same as the emulator's decisions and within 1e-12 in the sums"""
+    """at most 64 rows: the 64-thread instance of the same kernel, bitwise the same as the emulator's decisions and within 1e-12 in the sums"""
     pts, n, ref = _sets(7, P=64)
     for mf in (0, 20):
         _same(_run(tm.load(), "cuda", pts, n, ref, mf), _run(pc.emu_lib(), "cpu", pts, n, ref, mf), f"64 rows, max_front {mf}")

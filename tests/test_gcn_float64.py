@@ -250,7 +250,10 @@ def _check_aggregate_float64(lib, device):
             mut = G.act64(Ad @ G.f64(h) + G.f64(bias), act)
             assert not G.within(mut, ref, mag, TAU["agg"]), f"{label}: mutant without the diagonal passes"
 
-    for n, c, B in ((24, 70, 9), (32, 224, 5), (48, 36, 3), (64, 8, 4), (17, 4, 11)):
+    # the first five: the slab kernel and aggregate_kernel<32>; then aggregate4<16> over 3 blocks (C4 = 5 does not divide 256: graphs
+    # straddle the block boundaries) and in one block, aggregate_kernel<16> with one and two channel blocks, aggregate_kernel<64>
+    for n, c, B in ((24, 70, 9), (32, 224, 5), (48, 36, 3), (64, 8, 4), (17, 4, 11),
+                    (12, 20, 120), (8, 8, 70), (16, 6, 3), (9, 262, 2), (40, 6, 3)):
         h, bias = torch.randn(B, n, c, device=device), torch.randn(c, device=device)
         adj = torch.softmax(torch.randn(B, n, n, device=device), dim=-1)
         for a_, act in ((adj, "relu"), (adj[0], None), (adj, "sigmoid")):
