@@ -113,6 +113,13 @@ int truss_topo_fused_obs(const truss_topo_t *t);
  * +-1 -> sequential height repairs -> [symmetry] -> set_moveRange -> Model.gen_all -> objectives.
  * With TRUSS_F_NO_DECODE it is Model.restore(); Model.gen_all() + the objective sums of
  * Game_research04.__init__ (truss2D_ENV.py:264-274) = the reset path (_game_get_1_state :336-340).
+ *
+ * status[env] describes the LAST step only: every step (every step of truss_rollout too) overwrites it, so a design
+ * that one step flags and the next step's decode repairs comes back with 0 and correct results.  The float outputs
+ * of an env flagged TRUSS_STATUS_NOT_SPD (disp, q0, sr, point, obj, energy, reactions, the float64 copies and its
+ * slices of the observation tensors) are unspecified -- NaN as a rule; its design outputs (y_out, sec_out, move
+ * ranges) are valid.  The other envs of the batch are unaffected, bit for bit, whether they share a wavefront
+ * with the flagged env or not (tests/test_step_status.py).
  */
 #define TRUSS_STATUS_NOT_SPD 1
 #define TRUSS_STATUS_OBS_TIMEOUT 2

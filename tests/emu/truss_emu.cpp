@@ -23,6 +23,8 @@ struct float4 {
 // Test-only build (tests/test_solver_geometry.py): truss_emu_set_mutant(m) swaps one float64 shim for a float32 one, to prove
 // that the solver criteria of tests/fem_reference.py catch it.  1: pivot reciprocal rounded to float32 (no Newton refinement),
 // 2: 1/L of the elements in float32, 3: reactions accumulated in float32.  0: the plain emulator.
+// Mutants of the status fold (tests/test_step_status.py), in tb_group_max_f(., 2) below: 4: the bad-pivot flag is folded over the
+// 64 lanes of the wavefront instead of the env's G, 5: the fold returns 0.
 static int g_emu_mutant = 0;
 extern "C" int truss_emu_set_mutant(int m) {
   g_emu_mutant = m;
@@ -78,6 +80,13 @@ static inline double tb_group_sum_d(LN &ln, int which) {
 template <class LN>
 static inline float tb_group_max_f(LN &ln, int which) {
   float v = 0.0f;
+#ifdef TRUSS_EMU_MUTANTS
+  if (which == 2 && g_emu_mutant == 5) return 0.0f;
+  if (which == 2 && g_emu_mutant == 4) {
+    for (int j = 0; j < 64; ++j) v = fmaxf(v, (float)emu_peers(ln)[j].bad);
+    return v;
+  }
+#endif
   for (int j = 0; j < LN::G_; ++j) {
     const LN &p = emu_peers(ln)[ln.lane - ln.g + j];
     v = fmaxf(v, which == 0 ? p.p_c1 : which == 1 ? p.p_c2 : (float)p.bad);

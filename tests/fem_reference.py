@@ -61,8 +61,8 @@ def grids_for(ndof, e_lo, e_hi, n_mult4=True):
                     for r in (1, 0):
                         if 4 * nx - 4 + r - (nfix - pins) - 2 * pins == ndof:
                             yield supported_grid(nx, bool(r), nfix - pins, pins, prune)
-        if 2 * nx + 2 > ndof and full - (nx - 1) > e_hi:      # the fewest DOF / elements of this and every larger grid
-            return
+        if 2 * nx + 2 > ndof or full - (nx - 1) > e_hi:       # the fewest DOF / elements of this and every larger grid:
+            return                                            # either one past its limit ends the search
 
 
 def grid_for(ndof, e_lo, e_hi, n_mult4=True):
