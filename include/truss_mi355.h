@@ -265,6 +265,51 @@ typedef struct truss_front_args {
 
 int truss_front(const truss_front_args_t *args, void *stream);
 
+/* ---- difference reward of a game step, one launch for K (env, member) pairs ------------------------
+ * replaces: the reward block of master_DDPG_truss2D_MO.run() (:263-368, difference_reward): per pair the hypervolume of the
+ * archive plus the feasible new points with agent 0 / 1 / 2 left out and with all three (four culls), the archive's own
+ * hypervolume with and without the reference point, and the sums that turn them into the three agents' rewards, G_U and the
+ * running maxima -- what truss_mi355/reward.py::difference_reward assembles from three truss_front launches and about thirty
+ * element-wise operators.
+ *
+ * Per pair k:
+ *   agent j is feasible iff all four entries of points[k][j] are <= 1 (a NaN is infeasible)
+ *   set s (0..2) = the first n_front_no[k] rows of front_no[k] (clamped to [0, P]) + the feasible points of the agents other
+ *                  than s, in agent order; set 3 = the archive rows + all feasible points
+ *   every set goes through the cull, ordering, truncation and closed-form hypervolume of truss_front (above; max_front == 0:
+ *                  no truncation, else as TRUSS_FRONT_TRUNCATE) with the reference point ref_points[k]
+ *   sum_distance, std_cd = metrics [3], [4] of set 3
+ *   compareV / real_compareV = hv_all (truss_front) of the first n_pf_hv[k] rows of pf_hv[k] with ref_points[k] / with (1, 1)
+ *   R, G_U, xmax, ymax as in reward.py::difference_reward, float64, the same operations in the same order; no special case for
+ *                  n_pf == 0 or empty sets (IEEE results)
+ * DEVIATIONS from the per-env host path, both those of reward.py: (1) fronts longer than max_front are truncated
+ * deterministically (crowding distance), not with random.sample; (2) the final sum is float64 throughout, the reference's is
+ * float32 where an agent is feasible (NEP-50), so R agrees to ~1e-6 relative there.
+ * One workgroup per pair, the four sets on its four waves: P + 3 <= 64.  Device pointers; the library neither allocates nor
+ * synchronises (capturable in a hipGraph).  TRUSS_EINVAL: bad struct_size, n_sets < 0, max_points outside 1..61, max_front == 1
+ * (or < 0), a NULL input or R / G_U / xmax / ymax NULL; nothing is launched then.  n_sets == 0: TRUSS_OK, no launch.
+ * Optional symbol: a library of this ABI version may lack it. */
+typedef struct truss_reward_args {
+  size_t struct_size;
+  int32_t n_sets;            /* K: (env, member) pairs */
+  int32_t max_points;        /* P: row stride of front_no / pf_hv; P + 3 <= 64 */
+  int32_t max_front;         /* 0: no truncation; else as TRUSS_FRONT_TRUNCATE with this MAX_FRONT (>= 2) */
+  uint32_t flags;            /* 0 */
+  const double *front_no;    /* [K][P][4]  current non-dominated archive rows */
+  const int32_t *n_front_no; /* [K] */
+  const double *pf_hv;       /* [K][P][4]  archive rows the step started from; may alias front_no */
+  const int32_t *n_pf_hv;    /* [K] */
+  const double *parent;      /* [K][2]     (obj1, obj2) of the solution the agents acted on */
+  const double *points;      /* [K][3][4]  the three agents' new points */
+  const double *ref_points;  /* [K][2] */
+  const int32_t *n_pf;       /* [K]        len(Pf) */
+  double *R;                 /* [K][3] */
+  double *G_U, *xmax, *ymax; /* [K] */
+  double *parts;             /* [K][8] or NULL: hv(-0), hv(-1), hv(-2), hv(all), compareV, real_compareV, sum_distance, std_cd
+                                (the four hv BEFORE compareV is subtracted and clamped) */
+} truss_reward_args_t;
+int truss_reward(const truss_reward_args_t *args, void *stream);
+
 /* ---- GCN neighbourhood aggregation for the actors' inference in batched rollouts -----------------
  * replaces (inference only): the `A @ (X W) + b` + activation half of spektral GCNConv as used by
  * truss2D_RL.multimodes_actor (truss2D_RL.py:49-120): out[b][i][c] = act(sum_j A[b][i][j] H[b][j][c] + bias[c])

@@ -1,7 +1,7 @@
 // truss_torch_ops.cpp -- PyTorch custom operators in front of the C ABI of include/truss_mi355.h.
 //
 //   torch.ops.truss_mi355.step / rollout / obs / front / gcn_aggregate / gcn_aggregate_sparse / gcn_layer / gcn_level /
-//   gcn_level_backward / replay_scatter / replay_gather
+//   gcn_level_backward / replay_scatter / replay_gather / reward
 //
 // The reference's hot path runs inside TensorFlow ops on its side of the loop (truss2D_RL.py:328-354); here the env
 // step itself is an operator of the host framework: tensors in, tensors mutated in place, launched on the stream the
@@ -35,6 +35,7 @@ struct Backend {
   int (*gcn_level_bwd)(const truss_gcn_layer_args_t *, int32_t, const truss_gcn_level_bwd_t *, void *) = nullptr;
   int (*replay_scatter)(const truss_replay_field_t *, int32_t, const int64_t *, int32_t, int64_t, int64_t, void *) = nullptr;
   int (*replay_gather)(const truss_replay_field_t *, int32_t, const int64_t *, int32_t, int64_t, void *) = nullptr;
+  int (*reward)(const truss_reward_args_t *, void *) = nullptr;
   const char *(*last_error)(void) = nullptr;
   bool device = false;   // true: the HIP library (tensors must be on a cuda device)
 };
@@ -478,12 +479,57 @@ void replay_gather(int64_t lib, int64_t stream, at::TensorList ring, at::TensorL
 }
 void replay_gather_meta(int64_t, int64_t, at::TensorList, at::TensorList, const c10::List<OT> &, const at::Tensor &, int64_t) {}
 
+// the difference reward of K (env, member) pairs in one launch (master_DDPG_truss2D_MO.py:263-368) == truss_reward
+void reward(int64_t lib, int64_t stream, int64_t max_front, const at::Tensor &front_no, const at::Tensor &n_front_no, const at::Tensor &pf_hv,
+            const at::Tensor &n_pf_hv, const at::Tensor &parent, const at::Tensor &points, const at::Tensor &ref_points, const at::Tensor &n_pf,
+            const at::Tensor &R, const at::Tensor &G_U, const at::Tensor &xmax, const at::Tensor &ymax, const OT &parts) {
+  const Backend &b = backend(lib);
+  TORCH_CHECK(b.reward, "truss_mi355: the bound native library has no truss_reward");
+  TORCH_CHECK(front_no.dim() == 3 && front_no.size(2) == 4, "truss_mi355: front_no must be [K, P, 4]");
+  const int64_t K = front_no.size(0), P = front_no.size(1);
+  TORCH_CHECK(pf_hv.sizes() == front_no.sizes(), "truss_mi355: pf_hv must be [K, P, 4] like front_no");
+  TORCH_CHECK(P >= 1 && P + 3 <= 64, "truss_mi355: reward takes 1..61 archive rows per pair (P + 3 <= 64), got P = ", P);
+  TORCH_CHECK(max_front >= 0 && max_front <= INT32_MAX, "truss_mi355: max_front must be 0 or >= 2");
+  auto is1d = [K](const at::Tensor &t) { return t.dim() == 1 && t.size(0) == K; };
+  auto is2d = [K](const at::Tensor &t, int64_t c) { return t.dim() == 2 && t.size(0) == K && t.size(1) == c; };
+  TORCH_CHECK(is1d(n_front_no) && is1d(n_pf_hv) && is1d(n_pf), "truss_mi355: n_front_no / n_pf_hv / n_pf must be [K]");
+  TORCH_CHECK(is2d(parent, 2) && is2d(ref_points, 2), "truss_mi355: parent / ref_points must be [K, 2]");
+  TORCH_CHECK(points.dim() == 3 && points.size(0) == K && points.size(1) == 3 && points.size(2) == 4, "truss_mi355: points must be [K, 3, 4]");
+  TORCH_CHECK(is2d(R, 3), "truss_mi355: R must be [K, 3]");
+  TORCH_CHECK(is1d(G_U) && is1d(xmax) && is1d(ymax), "truss_mi355: G_U / xmax / ymax must be [K]");
+  TORCH_CHECK(!(parts.has_value() && parts->defined()) || is2d(*parts, 8), "truss_mi355: parts must be [K, 8]");
+  truss_reward_args_t a{};
+  a.struct_size = sizeof(truss_reward_args_t);
+  a.n_sets = (int32_t)K;
+  a.max_points = (int32_t)P;
+  a.max_front = (int32_t)max_front;
+  a.front_no = ptr<const double>(b, front_no, at::kDouble, "front_no");
+  a.n_front_no = ptr<const int32_t>(b, n_front_no, at::kInt, "n_front_no");
+  a.pf_hv = ptr<const double>(b, pf_hv, at::kDouble, "pf_hv");
+  a.n_pf_hv = ptr<const int32_t>(b, n_pf_hv, at::kInt, "n_pf_hv");
+  a.parent = ptr<const double>(b, parent, at::kDouble, "parent");
+  a.points = ptr<const double>(b, points, at::kDouble, "points");
+  a.ref_points = ptr<const double>(b, ref_points, at::kDouble, "ref_points");
+  a.n_pf = ptr<const int32_t>(b, n_pf, at::kInt, "n_pf");
+  a.R = ptr<double>(b, R, at::kDouble, "R");
+  a.G_U = ptr<double>(b, G_U, at::kDouble, "G_U");
+  a.xmax = ptr<double>(b, xmax, at::kDouble, "xmax");
+  a.ymax = ptr<double>(b, ymax, at::kDouble, "ymax");
+  a.parts = ptr<double>(b, parts, at::kDouble, "parts");
+  TORCH_CHECK(K <= INT32_MAX, "truss_mi355: too many pairs");
+  if (K == 0) return;
+  check_rc(b, b.reward(&a, (void *)stream), "truss_reward");
+}
+void reward_meta(int64_t, int64_t, int64_t, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &,
+                 const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &,
+                 const at::Tensor &, const OT &) {}
+
 }  // namespace
 
 // Bind the entry points of a loaded native library (addresses from ctypes) under a small index.
 extern "C" int truss_torch_bind(int lib, void *step_fn, void *rollout_fn, void *obs_fn, void *front_fn, void *gcn_fn, void *gcn_sparse_fn,
                                 void *gcn_layer_fn, void *gcn_split_fn, void *gcn_level_fn, void *gcn_level_bwd_fn, void *replay_scatter_fn,
-                                void *replay_gather_fn, void *last_error_fn, int is_device) {
+                                void *replay_gather_fn, void *reward_fn, void *last_error_fn, int is_device) {
   if (lib < 0 || lib >= (int)g_backends.size() || !step_fn) return -1;
   Backend &b = g_backends[lib];
   b.step = (decltype(b.step))step_fn;
@@ -498,6 +544,7 @@ extern "C" int truss_torch_bind(int lib, void *step_fn, void *rollout_fn, void *
   b.gcn_level_bwd = (decltype(b.gcn_level_bwd))gcn_level_bwd_fn;   // (may be null: a library without the entry)
   b.replay_scatter = (decltype(b.replay_scatter))replay_scatter_fn;   // (these two as well)
   b.replay_gather = (decltype(b.replay_gather))replay_gather_fn;
+  b.reward = (decltype(b.reward))reward_fn;                           // (and this one)
   b.last_error = (decltype(b.last_error))last_error_fn;
   b.device = is_device != 0;
   return 0;
@@ -531,6 +578,8 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("replay_scatter(int lib, int stream, Tensor(a!)[] ring, Tensor[] src, Tensor?[] nbr, int[] group, Tensor rows, int k, int head, "
         "int capacity) -> ()");
   m.def("replay_gather(int lib, int stream, Tensor[] ring, Tensor(a!)[] out, Tensor?[] nbr, Tensor idx, int capacity) -> ()");
+  m.def("reward(int lib, int stream, int max_front, Tensor front_no, Tensor n_front_no, Tensor pf_hv, Tensor n_pf_hv, Tensor parent, Tensor points, "
+        "Tensor ref_points, Tensor n_pf, Tensor(a!) R, Tensor(b!) G_U, Tensor(c!) xmax, Tensor(d!) ymax, Tensor(e!)? parts) -> ()");
 }
 TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) {   // the emulator library of the test-suite binds here
   m.impl("step", step);
@@ -545,6 +594,7 @@ TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) {   // the emulator library of the test-
   m.impl("gcn_level_backward", gcn_level_backward);
   m.impl("replay_scatter", replay_scatter);
   m.impl("replay_gather", replay_gather);
+  m.impl("reward", reward);
 }
 TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) {  // = HIP on ROCm: the product library
   m.impl("step", step);
@@ -559,6 +609,7 @@ TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) {  // = HIP on ROCm: the product librar
   m.impl("gcn_level_backward", gcn_level_backward);
   m.impl("replay_scatter", replay_scatter);
   m.impl("replay_gather", replay_gather);
+  m.impl("reward", reward);
 }
 TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {  // tracing: every operator only mutates its outputs
   m.impl("step", step_meta);
@@ -573,4 +624,5 @@ TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {  // tracing: every operator only muta
   m.impl("gcn_level_backward", gcn_level_backward_meta);
   m.impl("replay_scatter", replay_scatter_meta);
   m.impl("replay_gather", replay_gather_meta);
+  m.impl("reward", reward_meta);
 }

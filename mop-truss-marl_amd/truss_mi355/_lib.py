@@ -59,6 +59,17 @@ F_FRONT_TRUNCATE = 0x1
 FRONT_MAXP = 256
 
 
+class RewardArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_size_t), ("n_sets", C.c_int32), ("max_points", C.c_int32), ("max_front", C.c_int32),
+        ("flags", C.c_uint32), ("front_no", _vp), ("n_front_no", _vp), ("pf_hv", _vp), ("n_pf_hv", _vp), ("parent", _vp),
+        ("points", _vp), ("ref_points", _vp), ("n_pf", _vp), ("R", _vp), ("G_U", _vp), ("xmax", _vp), ("ymax", _vp), ("parts", _vp),
+    ]
+
+
+REWARD_MAXP = 61          # truss_reward: P archive rows + 3 new points on one 64-lane wave
+
+
 class TrussError(RuntimeError):
     pass
 
@@ -114,6 +125,10 @@ class TrussLib:
             d.truss_replay_scatter.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int64, C.c_int64, _vp]   # (truss_replay_field_t *: filled by the operators)
             d.truss_replay_gather.restype = C.c_int
             d.truss_replay_gather.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int64, _vp]
+        self.has_reward = hasattr(d, "truss_reward")                         # (optional: the difference reward as one launch)
+        if self.has_reward:
+            d.truss_reward.restype = C.c_int
+            d.truss_reward.argtypes = [C.POINTER(RewardArgs), _vp]
         d.truss_gcn_split_w.restype = C.c_int
         d.truss_gcn_split_w.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
         d.truss_gcn_aggregate_sparse.restype = C.c_int

@@ -7,7 +7,7 @@ once, every piece on the device:
     parents' analysis + observation   BatchedTruss.analyze / observe     (truss_step, truss_obs kernels)
     three agents' actions             truss2D_RL actors on a [B, N, .] batch (rocBLAS)
     the 3 B candidate designs         one truss_step launch over 3 B envs (+ truss_obs for the next states)
-    rewards                           reward.difference_reward            (truss_front kernel)
+    rewards                           reward.difference_reward            (truss_front kernel; reward_path="hip": truss_reward)
     archive update                    reward.front_hv + gathers
     replay + MADDPG update            device tensors, MADDPG.train_on_batch
 
@@ -570,8 +570,11 @@ class BatchedMARL:
     def __init__(self, topo: TrussTopology, n_envs: int, maddpg, *, max_front: int | None = None, lib=None, device=None,
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
                  pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None,
-                 level_backward: str | None = None, replay_storage: str | None = None):
-        """replay_storage: "dense" (the default) or "compact" (`DeviceReplay`: adjacencies stored through the neighbour tables, one
+                 level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None):
+        """reward_path: how a game step computes the difference reward of a chunk of pairs -- "torch" (three `truss_front` launches plus
+        element-wise operators, the default) or "hip" (one `truss_reward` launch; needs max_front + 3 <= 64 and a library with that
+        entry); None: "hip" if the environment has TRUSS_REWARD=hip, else "torch".
+        replay_storage: "dense" (the default) or "compact" (`DeviceReplay`: adjacencies stored through the neighbour tables, one
         launch per append / sample on the GPU); None: "compact" if the environment has TRUSS_REPLAY_STORAGE=compact, else "dense".
         level_backward: how the update differentiates a level of GCN layers on the GPU -- "library" (batched library GEMMs, the
         default) or "hip" (one `truss_gcn_level_backward` launch per level); None: "hip" if the environment has
@@ -615,6 +618,16 @@ class BatchedMARL:
         if replay_storage not in ("dense", "compact"):
             raise ValueError(f"replay_storage must be 'dense' or 'compact', got {replay_storage!r}")
         self.replay_storage = replay_storage
+        if reward_path is None:
+            reward_path = "hip" if os.environ.get("TRUSS_REWARD", "torch") == "hip" else "torch"
+        if reward_path not in ("torch", "hip"):
+            raise ValueError(f"reward_path must be 'torch' or 'hip', got {reward_path!r}")
+        if reward_path == "hip":
+            if not self.lib.has_reward:
+                raise ValueError(f"reward_path='hip': {self.lib.path} has no truss_reward")
+            if self.P + 3 > 64:
+                raise ValueError(f"reward_path='hip': max_front {self.P} + 3 new points exceed the 64 rows of a wave (truss_reward)")
+        self.reward_path = reward_path
         if self.device.type == "cuda":
             import truss2D_RL
             truss2D_RL.set_level_backward(_level_backward_hook(self.lib) if level_backward == "hip" else None, "cuda")
@@ -885,7 +898,7 @@ class BatchedMARL:
                 cand_y = eC.y[:3 * K].view(3, K, -1).permute(1, 0, 2)
                 cand_sec = eC.sec[:3 * K].view(3, K, -1).permute(1, 0, 2)
                 R, G_U, _, _ = RW.difference_reward(p0, nn0, p0, nn0, p0[ark, ms, :2].contiguous(), points, self.ref_points[idx].contiguous(),
-                                                    nn0, max_front=P, lib=self.lib)
+                                                    nn0, max_front=P, lib=self.lib, path=self.reward_path)
                 rsum.index_add_(0, idx, R)
                 tk = self._tick("reward", tk)
                 ok = (points[:, :, 2:4] <= 1).all(dim=2)                                      # archive candidates (:372)

@@ -1,9 +1,11 @@
 """torch.ops.truss_mi355.* -- the env step as PyTorch custom operators.
 
-`csrc/truss_torch_ops.cpp` registers `step`, `rollout`, `obs`, `front`, `gcn_aggregate`, `gcn_aggregate_sparse`, `gcn_layer`, `gcn_level`, `gcn_level_backward`, `replay_scatter` and `replay_gather` with the dispatcher
+`csrc/truss_torch_ops.cpp` registers `step`, `rollout`, `obs`, `front`, `gcn_aggregate`, `gcn_aggregate_sparse`, `gcn_layer`, `gcn_level`, `gcn_level_backward`, `replay_scatter`, `replay_gather` and `reward` with the dispatcher
 (CPU / CUDA(=HIP) / Meta keys): tensors in, outputs mutated in place, launched on the stream the caller names,
 capturable in a hipGraph, traceable.  The operators do no arithmetic; they call the C ABI of the native library that
-`bind()` registered under an index -- the HIP product library, or (test-suite only) the CPU lane emulator.
+`bind()` registered under an index -- the HIP product library, or (test-suite only) the CPU lane emulator.  Entry points a
+library may lack (`truss_gcn_level_backward`, the replay pair, `truss_reward`) are bound as null; their operators then fail
+with "the bound native library has no ...".
 
 There is no fallback: without `libtruss_torch_ops.so` (built by `make -C mop-truss-marl_amd/csrc`) loading fails.
 """
@@ -30,7 +32,7 @@ def _load():
         torch.ops.load_library(OPS_LIB)              # runs the TORCH_LIBRARY registrations
         _dll = C.CDLL(OPS_LIB)                       # the same image: for truss_torch_bind
         _dll.truss_torch_bind.restype = C.c_int
-        _dll.truss_torch_bind.argtypes = [C.c_int] + [C.c_void_p] * 13 + [C.c_int]
+        _dll.truss_torch_bind.argtypes = [C.c_int] + [C.c_void_p] * 14 + [C.c_int]
     return _dll
 
 
@@ -46,6 +48,7 @@ def bind(lib: "_lib.TrussLib") -> int:
                                   addr(d.truss_gcn_level_backward) if lib.has_level_backward else None,   # (the emulator has none)
                                   addr(d.truss_replay_scatter) if lib.has_replay_ops else None,
                                   addr(d.truss_replay_gather) if lib.has_replay_ops else None,
+                                  addr(d.truss_reward) if lib.has_reward else None,
                                   addr(d.truss_last_error),
                                   1 if lib.backend == "hip" else 0)
         if rc != 0:

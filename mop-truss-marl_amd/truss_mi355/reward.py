@@ -5,7 +5,9 @@ a23-a25) for B envs at once.
 simple_cull_final + utils.union_rectangles_fastest for a batch of small point sets, one wave per env.
 `difference_reward` restates the reward block of master_DDPG_truss2D_MO.run() (:263-368) on top of it:
 three launches (the three leave-one-agent-out fronts and the full front as one batch of 4 B point sets, and the archive's own
-hypervolume with and without the reference point) plus a few elementwise float64 torch ops.
+hypervolume with and without the reference point) plus a few elementwise float64 torch ops.  With `path="hip"` the whole
+block is ONE launch of the C entry `truss_reward` (csrc/truss_reward.h: one workgroup per pair, the four point sets on its four
+waves, the same float64 operations in the same order); `difference_reward_parts` also returns its intermediate values.
 
 Deviations from the per-env host path (master_DDPG_truss2D_MO.difference_reward), both documented in the
 header: (1) fronts longer than MAX_FRONT are truncated deterministically, not with random.sample;
@@ -57,7 +59,33 @@ def _append(base, n_base, extra, use):
     return out, (n + c[:, -1]).to(torch.int32)
 
 
-def difference_reward(front_no, n_front_no, pf_hv, n_pf_hv, parent, points, ref_points, n_pf, max_front=20, lib=None):
+PARTS = ("hv_0", "hv_1", "hv_2", "hv_all", "compareV", "real_compareV", "sum_distance", "std_cd")    # columns of the parts tensor
+
+
+def difference_reward_parts(front_no, n_front_no, pf_hv, n_pf_hv, parent, points, ref_points, n_pf, max_front=20, lib=None, stream=None,
+                            parts=True):
+    """`difference_reward` as one `truss_reward` launch (the path="hip" of it).  Returns R [B,3], G_U [B], xmax [B], ymax [B] and
+    parts [B,8] (columns `PARTS`: the hypervolumes of the three leave-one-out sets and of the full set before compareV is
+    subtracted, compareV, real_compareV, sum_distance, std_cd); parts=False skips that output (None)."""
+    lib = lib or _lib.load()
+    f64 = torch.float64
+    B, P = front_no.shape[0], front_no.shape[1]
+    if P + 3 > 64:
+        raise ValueError(f"the fused reward takes at most {_lib.REWARD_MAXP} archive rows per pair (P + 3 <= 64), got P = {P}")
+    if not lib.has_reward:
+        raise _lib.TrussError(f"{lib.path} has no truss_reward (the fused difference reward)")
+    dev = front_no.device
+    R = torch.empty((B, 3), dtype=f64, device=dev)
+    G_U, xmax, ymax = (torch.empty((B,), dtype=f64, device=dev) for _ in range(3))
+    Q = torch.empty((B, 8), dtype=f64, device=dev) if parts else None
+    from . import ops
+    stream_i = ops.stream_of(dev) if stream is None else int(getattr(stream, "value", stream) or 0)
+    ops.call(ops.namespace().reward, ops.bind(lib), stream_i, int(max_front), front_no.contiguous(), n_front_no.contiguous(), pf_hv.contiguous(),
+             n_pf_hv.contiguous(), parent.contiguous(), points.to(f64).contiguous(), ref_points.contiguous(), n_pf.contiguous(), R, G_U, xmax, ymax, Q)
+    return R, G_U, xmax, ymax, Q
+
+
+def difference_reward(front_no, n_front_no, pf_hv, n_pf_hv, parent, points, ref_points, n_pf, max_front=20, lib=None, path="torch"):
     """Batched master_DDPG_truss2D_MO.difference_reward (:263-368).
 
     front_no [B,P,4] / n_front_no [B]   current non-dominated archive rows
@@ -65,7 +93,12 @@ def difference_reward(front_no, n_front_no, pf_hv, n_pf_hv, parent, points, ref_
     parent   [B,2]                      (obj1, obj2) of the solution the agents acted on
     points   [B,3,4]                    the three agents' new points
     ref_points [B,2], n_pf [B]          reference point schedule, len(Pf)
+    path       "torch": truss_front launches + torch operators (below); "hip": one truss_reward launch
     returns R [B,3], G_U [B], xmax [B], ymax [B]   (float64 device tensors)"""
+    if path == "hip":
+        return difference_reward_parts(front_no, n_front_no, pf_hv, n_pf_hv, parent, points, ref_points, n_pf, max_front, lib, parts=False)[:4]
+    if path != "torch":
+        raise ValueError(f"path must be 'torch' or 'hip', got {path!r}")
     f64 = torch.float64
     points = points.to(f64)
     feas = (points <= 1.0).all(dim=2)                                   # _feasible: all four entries <= 1
