@@ -189,8 +189,6 @@ extern "C" int truss_front(const truss_front_args_t *a, void *stream) {
     hipLaunchKernelGGL(truss_front_kernel<64>, dim3((unsigned)a->n_envs), dim3(64), 0, (hipStream_t)stream, *a);
   else
     hipLaunchKernelGGL(truss_front_kernel<256>, dim3((unsigned)a->n_envs), dim3(256), 0, (hipStream_t)stream, *a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("front kernel launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("front kernel launch failed: ");
 }
 #endif  // __HIPCC__

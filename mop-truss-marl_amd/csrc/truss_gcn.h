@@ -15,8 +15,52 @@
 //   MFMA: lane (row | col = l % 32, half h = l / 32) holds k = 8 h .. 8 h + 7 of its row / column (two ds_read_b128); step s of the
 //         eight multiplies k = s (lanes of half 0) and k = 8 + s (half 1): the order of a sum over k is free.
 // W (160 KB at 200 x 200) is re-read by every workgroup from L2; X is read once, `out` written once.
+//
+// On top the argument checks of truss_gcn_layer and truss_gcn_level (truss_gcn_level.h), shared with the plain loops of the CPU
+// test backend in tests/emu/truss_emu.cpp; below them, for the device compiler only, the kernels, their dispatch and the C entries.
 #pragma once
+#include <cstdint>
+#include <string>
 
+static int tb_fail(int code, const std::string &msg);
+
+#define TG_LEVEL_MAX_K_IN 256    // truss_gcn_level: the kernel's TGL_SLABS slabs of TGL_KS k's (truss_gcn_level.h asserts it)
+#define TG_KREG 9                // neighbourhood terms per row held in registers (a truss node joins <= 8 elements: <= 9 terms with the diagonal)
+
+// One layer's argument block as entry `what` takes it: truss_gcn_layer (n_nodes <= 256, any k_in: max_k_in 0), or -- `level` -- a layer of
+// truss_gcn_level (128, TG_LEVEL_MAX_K_IN), where an empty layer passes unread and there is neither accumulation into out nor a
+// split-weight product.  The two `level` rules sit where truss_gcn_level has always applied them: the order of the checks decides
+// which text a doubly invalid block gets, and that text is part of the library's behaviour.
+static inline int tb_gcn_layer_check(const truss_gcn_layer_args_t *a, const char *what, int max_nodes, int max_k_in, bool level) {
+  auto fail = [what](int code, const std::string &msg) { return tb_fail(code, what + msg); };
+  if (a->struct_size != sizeof(truss_gcn_layer_args_t)) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer_args_t size mismatch (ABI)");
+  if (level && a->n_batch == 0) return TRUSS_OK;           // nothing to read, nothing to write
+  if (!a->x || !a->adj || !a->w || !a->out) return fail(TRUSS_EINVAL, ": a required pointer is NULL");
+  if (a->n_batch < 0 || a->n_nodes < 1 || a->k_in < 1 || a->c_out < 1 || a->act < 0 || a->act > 2) return fail(TRUSS_EINVAL, ": bad sizes / act");
+  if (level && (a->accumulate || a->w_bf16x3)) return fail(TRUSS_EUNSUPPORTED, ": float32 product, no accumulation into out");
+  if (a->c_out > 224) return fail(TRUSS_EUNSUPPORTED, level ? ": c_out <= 224" : ": c_out <= 224 (the reference's hidden width is 200)");
+  if (a->n_nodes > max_nodes) return fail(TRUSS_EUNSUPPORTED, ": n_nodes <= " + std::to_string(max_nodes));
+  if (max_k_in && a->k_in > max_k_in) return fail(TRUSS_EUNSUPPORTED, ": k_in <= " + std::to_string(max_k_in));
+  if (a->nbr ? (a->k_nbr < 1 || a->k_nbr > 16) : a->n_nodes > 64)
+    return fail(TRUSS_EUNSUPPORTED, ": a sparsity pattern of 1..16 terms per row, or a dense adjacency of at most 64 nodes");
+  if (a->x == a->out) return fail(TRUSS_EINVAL, ": out must not alias x");
+  return TRUSS_OK;
+}
+
+// x may be read in 16-byte pieces: alignment, and every 4-float chunk of a row whole or past the end
+static inline bool tb_gcn_x_vec(const truss_gcn_layer_args_t *a) {
+  return (size_t)a->x % 16 == 0 && (a->x_row_stride ? a->x_row_stride : a->k_in) % 4 == 0 && a->k_in % 4 == 0;
+}
+
+// The envelope of the bf16x3 product (truss_gcn_layer with split weights).  A shape outside it is an error, not a silent change of
+// arithmetic: the caller asked for this path by passing split weights.
+static inline int tb_gcn_bf16x3_check(const truss_gcn_layer_args_t *a) {
+  if (a->c_out <= 32 || !tb_gcn_x_vec(a) || (a->nbr ? a->k_nbr : a->n_nodes) > TG_KREG || ((size_t)a->w_bf16x3 & 15) != 0)
+    return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: the bf16x3 path takes c_out 33..224, k_in % 4 == 0, 16-byte aligned x / split weights, <= 9 terms per row");
+  return TRUSS_OK;
+}
+
+#ifdef __HIPCC__
 typedef float tg_f4 __attribute__((ext_vector_type(4)));
 typedef float tg_f16 __attribute__((ext_vector_type(16)));
 
@@ -47,8 +91,6 @@ __device__ unsigned long long g_gcn_stamps[8];
 #else
 #define TG_T(v)
 #endif
-
-#define TG_KREG 9                // neighbourhood terms per row held in registers (a truss node joins <= 8 elements: <= 9 terms with the diagonal)
 
 // VEC: x and w are 16-byte aligned with k_in % 4 == 0 -- every 4-float chunk of a slab is either whole or past the end, so the loads
 // are branch-free 16-byte loads from clamped addresses; otherwise (the 13-feature input layers) element-wise guarded loads.
@@ -606,18 +648,8 @@ static size_t tg_lds_bytes(int NW, int CB, int N, int Kn) {
   return (b + 15) & ~(size_t)15;
 }
 
-extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
-  if (!a) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: NULL argument");
-  if (a->struct_size != sizeof(truss_gcn_layer_args_t)) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer_args_t size mismatch (ABI)");
-  if (!a->x || !a->adj || !a->w || !a->out) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: a required pointer is NULL");
-  if (a->n_batch < 0 || a->n_nodes < 1 || a->k_in < 1 || a->c_out < 1 || a->act < 0 || a->act > 2)
-    return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: bad sizes / act");
-  if (a->c_out > 224) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: c_out <= 224 (the reference's hidden width is 200)");
-  if (a->n_nodes > 256) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: n_nodes <= 256");
-  if (a->nbr ? (a->k_nbr < 1 || a->k_nbr > 16) : a->n_nodes > 64)
-    return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: a sparsity pattern of 1..16 terms per row, or a dense adjacency of at most 64 nodes");
-  if (a->x == a->out) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: out must not alias x");
-  if (a->n_batch == 0) return TRUSS_OK;
+// the layer as the kernels take it; tile_rows: rows of a workgroup's tile (whole graphs)
+static GcnLayerDev tg_layer_dev(const truss_gcn_layer_args_t *a, int tile_rows) {
   GcnLayerDev P;
   P.x = a->x; P.adj = a->adj; P.nbr = a->nbr; P.w = a->w; P.bias = a->bias; P.out = a->out;
   P.x_stride = a->x_row_stride ? a->x_row_stride : a->k_in;
@@ -625,17 +657,23 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
   P.a_stride = a->a_batch_stride;
   P.B = a->n_batch; P.N = a->n_nodes; P.K = a->k_in; P.C = a->c_out; P.act = a->act; P.accumulate = a->accumulate ? 1 : 0;
   P.Kn = a->nbr ? a->k_nbr : a->n_nodes;
-  const int NW = a->n_nodes > 128 ? 8 : 4, MT = 32 * NW;
-  P.GB = MT / a->n_nodes;
-  P.x_vec = ((size_t)a->x % 16 == 0 && P.x_stride % 4 == 0 && a->k_in % 4 == 0) ? 1 : 0;
+  P.GB = tile_rows / a->n_nodes;
+  P.x_vec = tb_gcn_x_vec(a) ? 1 : 0;
   P.w_vec = ((size_t)a->w % 16 == 0 && a->k_in % 4 == 0) ? 1 : 0;
+  return P;
+}
+
+extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
+  if (!a) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: NULL argument");
+  if (int rc = tb_gcn_layer_check(a, "truss_gcn_layer", 256, 0, false)) return rc;
+  if (a->n_batch == 0) return TRUSS_OK;
+  const int NW = a->n_nodes > 128 ? 8 : 4;
+  const GcnLayerDev P = tg_layer_dev(a, 32 * NW);
   const int CB = a->c_out <= 32 ? 1 : 7;
   hipStream_t st = (hipStream_t)stream;
   if (a->w_bf16x3) {
-    // product on the bf16 matrix cores at float32 accuracy (see truss_gcn_layer_bf3_kernel); shapes outside its envelope are an error,
-    // not a silent change of arithmetic: the caller asked for this path by passing split weights
-    if (CB != 7 || !(P.x_vec) || P.Kn > TG_KREG || ((size_t)a->w_bf16x3 & 15) != 0)
-      return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: the bf16x3 path takes c_out 33..224, k_in % 4 == 0, 16-byte aligned x / split weights, <= 9 terms per row");
+    // product on the bf16 matrix cores at float32 accuracy (see truss_gcn_layer_bf3_kernel)
+    if (int rc = tb_gcn_bf16x3_check(a)) return rc;
     const int KP = (a->k_in + 15) & ~15;
     const size_t MTb = 32 * (size_t)NW;
     const size_t lds3 = MTb * TG_LD * 4 + 2 * 3 * MTb * 32 + 2 * 3 * 224 * 32;
@@ -649,9 +687,7 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
     if (NW == 4) { if (P.Kn <= 6) TG_LAUNCH3(4, 6); else TG_LAUNCH3(4, 9); }
     else { if (P.Kn <= 6) TG_LAUNCH3(8, 6); else TG_LAUNCH3(8, 9); }
 #undef TG_LAUNCH3
-    hipError_t e3 = hipGetLastError();
-    if (e3 != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn layer (bf16x3) kernel launch failed: ") + hipGetErrorString(e3));
-    return TRUSS_OK;
+    return tb_launched("gcn layer (bf16x3) kernel launch failed: ");
   }
   const size_t lds = tg_lds_bytes(NW, CB, a->n_nodes, P.Kn);
   if (lds > 160 * 1024) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: tile does not fit the LDS");
@@ -668,9 +704,7 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
   else if (CB == 7) { if (vec) TG_LAUNCH(8, 7, true); else TG_LAUNCH(8, 7, false); }
   else { if (vec) TG_LAUNCH(8, 1, true); else TG_LAUNCH(8, 1, false); }
 #undef TG_LAUNCH
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn layer kernel launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("gcn layer kernel launch failed: ");
 }
 
 #ifdef TRUSS_GCN_STAMPS
@@ -685,7 +719,6 @@ extern "C" int truss_gcn_split_w(const float *w, int32_t c_out, int32_t k_in, ui
   const int KP = (k_in + 15) & ~15;
   const int n = TG_CP * KP;
   hipLaunchKernelGGL(truss_gcn_split_w_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, w_bf16x3, c_out, k_in, KP);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn split kernel launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("gcn split kernel launch failed: ");
 }
+#endif  // __HIPCC__

@@ -215,18 +215,14 @@ extern "C" int truss_gcn_aggregate_sparse(const float *adj, int64_t a_batch_stri
   // over its 32 KB tile and loses: 52 against 42 us, tools/agg_probe.py)
   if (n_nodes <= tb_env_int("TRUSS_GCN_SLAB_MAX_N", 128) &&
       tb_launch_gcn_slab(adj, a_batch_stride, nbr, k_nbr, h, bias, out, n_batch, n_nodes, n_channels, act, (hipStream_t)stream)) {
-    hipError_t es = hipGetLastError();
-    if (es != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn slab aggregate launch failed: ") + hipGetErrorString(es));
-    return TRUSS_OK;
+    return tb_launched("gcn slab aggregate launch failed: ");
   }
   const int C4 = n_channels / 4;
   const long total = (long)n_batch * n_nodes * C4;
   const dim3 grid((unsigned)((total + 255) / 256));
   const auto kern = k_nbr <= 4 ? truss_gcn_aggregate_sparse_kernel<4> : k_nbr <= 8 ? truss_gcn_aggregate_sparse_kernel<8> : truss_gcn_aggregate_sparse_kernel<12>;
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, adj, (long)a_batch_stride, nbr, k_nbr, h, bias, out, total, n_nodes, C4, act);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn sparse aggregate launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("gcn sparse aggregate launch failed: ");
 }
 
 extern "C" int truss_gcn_aggregate(const float *adj, int64_t a_batch_stride, const float *h, const float *bias, float *out,
@@ -236,9 +232,7 @@ extern "C" int truss_gcn_aggregate(const float *adj, int64_t a_batch_stride, con
   // 17..64 nodes: the slab kernel (32 nodes: 58-61 us against 73-84 for the channel-quad kernel below, 64 nodes: 44 against 182 for
   // the thread-per-channel kernel and 75 for rocBLAS + bias + activation); <= 16 nodes: the channel-quad kernel (56 against 74 us)
   if (n_nodes > tb_env_int("TRUSS_GCN_SLAB_DENSE_ABOVE", 16) && tb_launch_gcn_slab(adj, a_batch_stride, nullptr, n_nodes, h, bias, out, n_batch, n_nodes, n_channels, act, (hipStream_t)stream)) {
-    hipError_t es = hipGetLastError();
-    if (es != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn slab aggregate launch failed: ") + hipGetErrorString(es));
-    return TRUSS_OK;
+    return tb_launched("gcn slab aggregate launch failed: ");
   }
   if ((n_channels & 3) == 0 && n_nodes <= 32 && (((size_t)h | (size_t)out | (size_t)bias) & 15) == 0) {
     // channel-quad threads, no idle lanes
@@ -250,16 +244,12 @@ extern "C" int truss_gcn_aggregate(const float *adj, int64_t a_batch_stride, con
     if (lds <= 64 * 1024) {
       const auto kern4 = n_nodes <= 16 ? truss_gcn_aggregate4_kernel<16> : truss_gcn_aggregate4_kernel<32>;
       hipLaunchKernelGGL(kern4, dim3(blocks), dim3(256), lds, (hipStream_t)stream, adj, (long)a_batch_stride, h, bias, out, n_batch, n_nodes, C4, act, gmax);
-      hipError_t e4 = hipGetLastError();
-      if (e4 != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn aggregate launch failed: ") + hipGetErrorString(e4));
-      return TRUSS_OK;
+      return tb_launched("gcn aggregate launch failed: ");
     }
   }
   dim3 grid((unsigned)n_batch, (unsigned)((n_channels + 255) / 256));
   const auto kern = n_nodes <= 16 ? truss_gcn_aggregate_kernel<16> : n_nodes <= 32 ? truss_gcn_aggregate_kernel<32> : truss_gcn_aggregate_kernel<64>;
   hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, adj, (long)a_batch_stride, h, bias, out, n_nodes, n_channels, act);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn aggregate launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("gcn aggregate launch failed: ");
 }
 #endif  // __HIPCC__

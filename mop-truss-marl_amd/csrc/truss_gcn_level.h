@@ -22,6 +22,7 @@ struct GcnLevelDev {
 #define TGL_LD 68                // floats per LDS row of a slab (64 + 4 padding: rows 272 bytes apart)
 #define TGL_HLD 36               // floats per LDS row of the 128 x 32 product tile (32 + 4 padding: rows 144 bytes apart)
 #define TGL_SLABS 4              // slabs of the product (three requested up front, the fourth behind the first): k_in <= 256
+static_assert(TGL_SLABS * TGL_KS == TG_LEVEL_MAX_K_IN, "the level's k_in limit, as the shared argument check has it");
 
 #ifdef TRUSS_GCN_STAMPS   // diagnostic build: shader-clock stamps of block (0, 0, 0) / thread 0 (tools/gcn_level_probe.py)
 __device__ unsigned long long g_level_stamps[8];
@@ -308,21 +309,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TGL_WAVES_P
 
 extern "C" int truss_gcn_level(const truss_gcn_layer_args_t *layers, int32_t n_layers, float *const *x_agg, void *stream) {
   if (n_layers < 0 || (n_layers > 0 && !layers)) return tb_fail(TRUSS_EINVAL, "truss_gcn_level: bad argument");
-  for (int i = 0; i < n_layers; ++i) {
-    const truss_gcn_layer_args_t *a = layers + i;
-    if (a->struct_size != sizeof(truss_gcn_layer_args_t)) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer_args_t size mismatch (ABI)");
-    if (a->n_batch == 0) continue;                           // an empty layer: nothing to read, nothing to write
-    if (!a->x || !a->adj || !a->w || !a->out) return tb_fail(TRUSS_EINVAL, "truss_gcn_level: a required pointer is NULL");
-    if (a->n_batch < 0 || a->n_nodes < 1 || a->k_in < 1 || a->c_out < 1 || a->act < 0 || a->act > 2)
-      return tb_fail(TRUSS_EINVAL, "truss_gcn_level: bad sizes / act");
-    if (a->accumulate || a->w_bf16x3) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_level: float32 product, no accumulation into out");
-    if (a->c_out > 224) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_level: c_out <= 224");
-    if (a->n_nodes > 128) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_level: n_nodes <= 128");
-    if (a->k_in > TGL_SLABS * TGL_KS) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_level: k_in <= 256");
-    if (a->nbr ? (a->k_nbr < 1 || a->k_nbr > 16) : a->n_nodes > 64)
-      return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_level: a sparsity pattern of 1..16 terms per row, or a dense adjacency of at most 64 nodes");
-    if (a->x == a->out) return tb_fail(TRUSS_EINVAL, "truss_gcn_level: out must not alias x");
-  }
+  for (int i = 0; i < n_layers; ++i)
+    if (int rc = tb_gcn_layer_check(layers + i, "truss_gcn_level", 128, TG_LEVEL_MAX_K_IN, true)) return rc;
   hipStream_t st = (hipStream_t)stream;
   for (int i0 = 0; i0 < n_layers; i0 += TGL_MAX) {
     const int nl = n_layers - i0 < TGL_MAX ? n_layers - i0 : TGL_MAX;
@@ -335,16 +323,7 @@ extern "C" int truss_gcn_level(const truss_gcn_layer_args_t *layers, int32_t n_l
     for (int i = 0; i < nl; ++i) {
       const truss_gcn_layer_args_t *a = layers + i0 + i;
       if (a->n_batch == 0) continue;
-      GcnLayerDev &P = LV.l[live];
-      P.x = a->x; P.adj = a->adj; P.nbr = a->nbr; P.w = a->w; P.bias = a->bias; P.out = a->out;
-      P.x_stride = a->x_row_stride ? a->x_row_stride : a->k_in;
-      P.out_stride = a->out_row_stride ? a->out_row_stride : a->c_out;
-      P.a_stride = a->a_batch_stride;
-      P.B = a->n_batch; P.N = a->n_nodes; P.K = a->k_in; P.C = a->c_out; P.act = a->act; P.accumulate = 0;
-      P.Kn = a->nbr ? a->k_nbr : a->n_nodes;
-      P.GB = 128 / a->n_nodes;
-      P.x_vec = ((size_t)a->x % 16 == 0 && P.x_stride % 4 == 0 && a->k_in % 4 == 0) ? 1 : 0;
-      P.w_vec = ((size_t)a->w % 16 == 0 && a->k_in % 4 == 0) ? 1 : 0;
+      const GcnLayerDev &P = LV.l[live] = tg_layer_dev(a, 128);
       LV.xagg[live] = x_agg ? x_agg[i0 + i] : nullptr;
       const size_t tb = (!a->nbr && P.Kn <= 16) ? 0 : sizeof(float) * 128 * (size_t)P.Kn + sizeof(int16_t) * (size_t)a->n_nodes * P.Kn;
       tables = tb > tables ? tb : tables;
@@ -366,8 +345,7 @@ extern "C" int truss_gcn_level(const truss_gcn_layer_args_t *layers, int32_t n_l
     static TbLdsOptIn optin;
     if (int rc = optin.ensure((const void *)truss_gcn_level_kernel)) return rc;
     hipLaunchKernelGGL(truss_gcn_level_kernel, dim3(tiles, (unsigned)live, cbs + xslabs), dim3(256), lds, st, LV, (int)cbs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn level kernel launch failed: ") + hipGetErrorString(e));
+    if (int rc = tb_launched("gcn level kernel launch failed: ")) return rc;
   }
   return TRUSS_OK;
 }

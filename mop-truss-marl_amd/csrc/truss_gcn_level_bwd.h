@@ -353,8 +353,7 @@ extern "C" int truss_gcn_level_backward(const truss_gcn_layer_args_t *layers, in
     static TbLdsOptIn optin;
     if (int rc = optin.ensure((const void *)truss_gcn_level_bwd_kernel)) return rc;
     hipLaunchKernelGGL(truss_gcn_level_bwd_kernel, dim3(slices, (unsigned)live), dim3(256), lds, st, LV);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("gcn level backward kernel launch failed: ") + hipGetErrorString(e));
+    if (int rc = tb_launched("gcn level backward kernel launch failed: ")) return rc;
   }
   return TRUSS_OK;
 }

@@ -403,14 +403,17 @@ struct TbLdsOptIn {
     return TRUSS_OK;
   }
 };
+// behind every kernel launch: TRUSS_OK, or TRUSS_EHIP with `what` (the site's own "... launch failed: ") + HIP's error text
+static int tb_launched(const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? TRUSS_OK : tb_fail(TRUSS_EHIP, std::string(what) + hipGetErrorString(e));
+}
 
 static int tb_launch_obs(const truss_topo *t, const ObsArgsDev &A, void *stream) {
   static TbLdsOptIn optin;
   if (int rc = optin.ensure((const void *)truss_obs_kernel)) return rc;
   hipLaunchKernelGGL(truss_obs_kernel, dim3((unsigned)A.B, (unsigned)(A.n_split > 1 ? A.n_split + 1 : 1)), dim3(64), tb_obs_lds_bytes(t->N), (hipStream_t)stream, t->dev, A);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("obs kernel launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("obs kernel launch failed: ");
 }
 
 template <int G, int WL, int RPL, int EPL, bool EMIT>
@@ -421,9 +424,7 @@ static int hip_run(const truss_topo *t, const StepArgsDev &A, hipStream_t st) {
   constexpr int EPB = 64 / G;
   const unsigned grid = (unsigned)((A.B + EPB - 1) / EPB);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(EMIT ? 128 : 64), EMIT ? t->lds_bytes_emit : t->lds_bytes, st, EMIT ? t->dev_emit : t->dev, A);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("kernel launch failed: ");
 }
 
 template <int G, int WL, int RPL, int EPL>
@@ -441,9 +442,7 @@ static int hip_run_rollout(const truss_topo *t, const StepArgsDev &A, int n_step
   constexpr int EPB = 64 / G;
   const unsigned grid = (unsigned)((A.B + EPB - 1) / EPB);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64), t->lds_bytes, st, Q);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("rollout kernel launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("rollout kernel launch failed: ");
 }
 static int tb_launch_rollout(const truss_topo *t, const StepArgsDev &A, int n_steps, int n_sets, void *stream) {
   const TbVariant &v = kVariants[t->variant];

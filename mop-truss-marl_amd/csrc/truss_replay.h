@@ -190,8 +190,7 @@ static int trp_run(const char *what, bool gather, const truss_replay_field_t *fi
       hipLaunchKernelGGL(truss_replay_kernel<true>, dim3(gx, (unsigned)nf), dim3(256), 0, st, D);
     else
       hipLaunchKernelGGL(truss_replay_kernel<false>, dim3(gx, (unsigned)nf), dim3(256), 0, st, D);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return tb_fail(TRUSS_EHIP, me + " kernel launch failed: " + hipGetErrorString(e));
+    if (int rc = tb_launched((me + " kernel launch failed: ").c_str())) return rc;
   }
   return TRUSS_OK;
 }

@@ -224,8 +224,6 @@ extern "C" int truss_reward(const truss_reward_args_t *a, void *stream) {
   if (int rc = tb_reward_check(a)) return rc;
   if (a->n_sets == 0) return TRUSS_OK;
   hipLaunchKernelGGL(truss_reward_kernel, dim3((unsigned)a->n_sets), dim3(256), 0, (hipStream_t)stream, *a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tb_fail(TRUSS_EHIP, std::string("reward kernel launch failed: ") + hipGetErrorString(e));
-  return TRUSS_OK;
+  return tb_launched("reward kernel launch failed: ");
 }
 #endif  // __HIPCC__

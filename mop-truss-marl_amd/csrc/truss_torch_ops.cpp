@@ -1,7 +1,5 @@
-// truss_torch_ops.cpp -- PyTorch custom operators in front of the C ABI of include/truss_mi355.h.
-//
-//   torch.ops.truss_mi355.step / rollout / obs / front / gcn_aggregate / gcn_aggregate_sparse / gcn_layer / gcn_level /
-//   gcn_level_backward / replay_scatter / replay_gather / reward
+// truss_torch_ops.cpp -- PyTorch custom operators in front of the C ABI of include/truss_mi355.h: one operator of
+// torch.ops.truss_mi355 per line of TRUSS_OPERATOR_ENTRIES below.
 //
 // The reference's hot path runs inside TensorFlow ops on its side of the loop (truss2D_RL.py:328-354); here the env
 // step itself is an operator of the host framework: tensors in, tensors mutated in place, launched on the stream the
@@ -13,30 +11,41 @@
 #include <torch/library.h>
 #include <ATen/ATen.h>
 
+#include <dlfcn.h>
+
 #include <array>
+#include <cstring>
 #include <vector>
 #include <string>
 
 #include "../../include/truss_mi355.h"
 
+// THE table of native entry points: X(field, symbol, required).  `field` is the member of Backend and, for the
+// operator entries, the name of the operator (and of the function below that implements it); `symbol` is looked up by
+// name in the bound library, its pointer type comes from the header's declaration.  A library may lack the optional
+// ones (the CPU lane emulator does): their operators then fail with "the bound native library has no <symbol>".
+#define TRUSS_OPERATOR_ENTRIES(X)                                \
+  X(step, truss_step, true)                                      \
+  X(rollout, truss_rollout, true)                                \
+  X(obs, truss_obs, true)                                        \
+  X(front, truss_front, true)                                    \
+  X(gcn_aggregate, truss_gcn_aggregate, true)                    \
+  X(gcn_aggregate_sparse, truss_gcn_aggregate_sparse, true)      \
+  X(gcn_layer, truss_gcn_layer, true)                            \
+  X(gcn_split_w, truss_gcn_split_w, true)                        \
+  X(gcn_level, truss_gcn_level, true)                            \
+  X(gcn_level_backward, truss_gcn_level_backward, false)         \
+  X(replay_scatter, truss_replay_scatter, false)                 \
+  X(replay_gather, truss_replay_gather, false)                   \
+  X(reward, truss_reward, false)
+#define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
+
 namespace {
 
 struct Backend {
-  int (*step)(const truss_topo_t *, const truss_step_args_t *, void *) = nullptr;
-  int (*rollout)(const truss_topo_t *, const truss_step_args_t *, int32_t, int32_t, void *) = nullptr;
-  int (*obs)(const truss_topo_t *, const truss_obs_args_t *, void *) = nullptr;
-  int (*front)(const truss_front_args_t *, void *) = nullptr;
-  int (*gcn)(const float *, int64_t, const float *, const float *, float *, int32_t, int32_t, int32_t, int32_t, void *) = nullptr;
-  int (*gcn_sparse)(const float *, int64_t, const int16_t *, int32_t, const float *, const float *, float *, int32_t, int32_t, int32_t,
-                    int32_t, void *) = nullptr;
-  int (*gcn_layer)(const truss_gcn_layer_args_t *, void *) = nullptr;
-  int (*gcn_split)(const float *, int32_t, int32_t, uint16_t *, void *) = nullptr;
-  int (*gcn_level)(const truss_gcn_layer_args_t *, int32_t, float *const *, void *) = nullptr;
-  int (*gcn_level_bwd)(const truss_gcn_layer_args_t *, int32_t, const truss_gcn_level_bwd_t *, void *) = nullptr;
-  int (*replay_scatter)(const truss_replay_field_t *, int32_t, const int64_t *, int32_t, int64_t, int64_t, void *) = nullptr;
-  int (*replay_gather)(const truss_replay_field_t *, int32_t, const int64_t *, int32_t, int64_t, void *) = nullptr;
-  int (*reward)(const truss_reward_args_t *, void *) = nullptr;
-  const char *(*last_error)(void) = nullptr;
+#define X(field, symbol, required) decltype(&symbol) field = nullptr;
+  TRUSS_ENTRY_POINTS(X)
+#undef X
   bool device = false;   // true: the HIP library (tensors must be on a cuda device)
 };
 std::array<Backend, 8> g_backends;
@@ -51,6 +60,10 @@ void check_rc(const Backend &b, int rc, const char *what) {
   TORCH_CHECK(rc == TRUSS_OK, what, " failed (", rc, "): ", b.last_error ? b.last_error() : "?");
 }
 
+using OT = c10::optional<at::Tensor>;
+bool present(const OT &t) { return t.has_value() && t->defined(); }
+OT at_or_none(const c10::List<OT> &l, size_t i) { return l.empty() ? OT() : l.get(i); }   // an empty list: no entry for any layer
+
 // data pointer of a tensor the ABI will read / write as `dtype`, nullptr for an absent optional
 template <typename T>
 T *ptr(const Backend &b, const at::Tensor &t, at::ScalarType dtype, const char *name, int64_t min_numel = 0) {
@@ -62,19 +75,29 @@ T *ptr(const Backend &b, const at::Tensor &t, at::ScalarType dtype, const char *
   return (T *)t.data_ptr();
 }
 template <typename T>
-T *ptr(const Backend &b, const c10::optional<at::Tensor> &t, at::ScalarType dtype, const char *name, int64_t min_numel = 0) {
-  return t.has_value() && t->defined() ? ptr<T>(b, *t, dtype, name, min_numel) : nullptr;
+T *ptr(const Backend &b, const OT &t, at::ScalarType dtype, const char *name, int64_t min_numel = 0) {
+  return present(t) ? ptr<T>(b, *t, dtype, name, min_numel) : nullptr;
 }
 
-using OT = c10::optional<at::Tensor>;
+// an optional entry point of the bound library
+template <typename F>
+void need(F fn, const char *symbol) {
+  TORCH_CHECK(fn, "truss_mi355: the bound native library has no ", symbol);
+}
+
+#define STEP_TENSOR_PARAMS                                                                                                     \
+  const at::Tensor &x, const at::Tensor &y_in, const at::Tensor &sec_in, const OT &max_up_in, const OT &max_down_in,          \
+      const OT &a_geo, const OT &a_topo, const OT &coin, const at::Tensor &target, const at::Tensor &env_params,              \
+      const at::Tensor &y_out, const OT &sec_out, const OT &max_up_out, const OT &max_down_out, const at::Tensor &disp,       \
+      const at::Tensor &q0, const at::Tensor &sr, const at::Tensor &comp, const at::Tensor &point, const OT &obj,             \
+      const OT &disp_f64, const OT &q0_f64, const OT &energy, const OT &reactions, const OT &status, const OT &x_n,           \
+      const OT &A_s, const OT &A_n_ts, const OT &A_n_cs, const OT &nN_x_n, const OT &nN_x_e
+#define STEP_TENSOR_ARGS                                                                                                       \
+  x, y_in, sec_in, max_up_in, max_down_in, a_geo, a_topo, coin, target, env_params, y_out, sec_out, max_up_out, max_down_out,  \
+      disp, q0, sr, comp, point, obj, disp_f64, q0_f64, energy, reactions, status, x_n, A_s, A_n_ts, A_n_cs, nN_x_n, nN_x_e
 
 void fill_step(const Backend &b, truss_step_args_t &a, int64_t flags, int64_t n_envs, int64_t N, int64_t E, int64_t sets,
-               const at::Tensor &x, const at::Tensor &y_in, const at::Tensor &sec_in, const OT &max_up_in, const OT &max_down_in,
-               const OT &a_geo, const OT &a_topo, const OT &coin, const at::Tensor &target, const at::Tensor &env_params,
-               const at::Tensor &y_out, const OT &sec_out, const OT &max_up_out, const OT &max_down_out, const at::Tensor &disp,
-               const at::Tensor &q0, const at::Tensor &sr, const at::Tensor &comp, const at::Tensor &point, const OT &obj,
-               const OT &disp_f64, const OT &q0_f64, const OT &energy, const OT &reactions, const OT &status, const OT &x_n,
-               const OT &A_s, const OT &A_n_ts, const OT &A_n_cs, const OT &nN_x_n, const OT &nN_x_e) {
+               STEP_TENSOR_PARAMS) {
   TORCH_CHECK(n_envs >= 1 && N >= 2 && E >= 1, "truss_mi355: bad n_envs / n_nodes / n_elems");
   const int64_t B = n_envs, BN = B * N, BE = B * E;
   const auto f32 = at::kFloat, f64 = at::kDouble, i32 = at::kInt, u8 = at::kByte;
@@ -115,17 +138,6 @@ void fill_step(const Backend &b, truss_step_args_t &a, int64_t flags, int64_t n_
   a.nN_x_e = ptr<float>(b, nN_x_e, f32, "nN_x_e", BE * 21);
 }
 
-#define STEP_TENSOR_PARAMS                                                                                                     \
-  const at::Tensor &x, const at::Tensor &y_in, const at::Tensor &sec_in, const OT &max_up_in, const OT &max_down_in,          \
-      const OT &a_geo, const OT &a_topo, const OT &coin, const at::Tensor &target, const at::Tensor &env_params,              \
-      const at::Tensor &y_out, const OT &sec_out, const OT &max_up_out, const OT &max_down_out, const at::Tensor &disp,       \
-      const at::Tensor &q0, const at::Tensor &sr, const at::Tensor &comp, const at::Tensor &point, const OT &obj,             \
-      const OT &disp_f64, const OT &q0_f64, const OT &energy, const OT &reactions, const OT &status, const OT &x_n,           \
-      const OT &A_s, const OT &A_n_ts, const OT &A_n_cs, const OT &nN_x_n, const OT &nN_x_e
-#define STEP_TENSOR_ARGS                                                                                                       \
-  x, y_in, sec_in, max_up_in, max_down_in, a_geo, a_topo, coin, target, env_params, y_out, sec_out, max_up_out, max_down_out,  \
-      disp, q0, sr, comp, point, obj, disp_f64, q0_f64, energy, reactions, status, x_n, A_s, A_n_ts, A_n_cs, nN_x_n, nN_x_e
-
 // One Game_research04._game_modify per env (truss2D_ENV.py:370-525) == truss_step
 void step(int64_t lib, int64_t topo, int64_t stream, int64_t flags, int64_t n_envs, int64_t n_nodes, int64_t n_elems,
           STEP_TENSOR_PARAMS) {
@@ -142,8 +154,6 @@ void rollout(int64_t lib, int64_t topo, int64_t stream, int64_t flags, int64_t n
   fill_step(b, a, flags, n_envs, n_nodes, n_elems, n_action_sets, STEP_TENSOR_ARGS);
   check_rc(b, b.rollout((const truss_topo_t *)topo, &a, (int32_t)n_steps, (int32_t)n_action_sets, (void *)stream), "truss_rollout");
 }
-void step_meta(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, STEP_TENSOR_PARAMS) {}
-void rollout_meta(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, STEP_TENSOR_PARAMS) {}
 
 // state_data + state_data_not_norm (truss2D_ENV.py:40-193) == truss_obs
 void obs(int64_t lib, int64_t topo, int64_t stream, int64_t n_envs, int64_t N, int64_t E, const at::Tensor &x, const at::Tensor &y,
@@ -176,9 +186,6 @@ void obs(int64_t lib, int64_t topo, int64_t stream, int64_t n_envs, int64_t N, i
   a.nN_x_e = ptr<float>(b, nN_x_e, f32, "nN_x_e", BE * 21);
   check_rc(b, b.obs((const truss_topo_t *)topo, &a, (void *)stream), "truss_obs");
 }
-void obs_meta(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, const at::Tensor &, const at::Tensor &, const at::Tensor &,
-              const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &,
-              const at::Tensor &, const at::Tensor &, const OT &, const OT &, const OT &, const OT &, const OT &, const OT &) {}
 
 // Pareto cull + 2-D hypervolume of B small point sets (utils.py:11-342) == truss_front
 void front(int64_t lib, int64_t stream, int64_t max_front, int64_t flags, const at::Tensor &points, const at::Tensor &n_points,
@@ -203,57 +210,17 @@ void front(int64_t lib, int64_t stream, int64_t max_front, int64_t flags, const 
   if (B == 0) return;
   check_rc(b, b.front(&a, (void *)stream), "truss_front");
 }
-void front_meta(int64_t, int64_t, int64_t, int64_t, const at::Tensor &, const at::Tensor &, const OT &, const OT &, const OT &, const OT &,
-                const OT &, const OT &) {}
 
-// act(A @ H + bias) of a GCN layer for B small graphs (truss2D_RL.py:49-120, inference) == truss_gcn_aggregate
-void gcn_aggregate(int64_t lib, int64_t stream, const at::Tensor &adj, const at::Tensor &h, const OT &bias, const at::Tensor &out,
-                   int64_t act) {
-  const Backend &b = backend(lib);
-  TORCH_CHECK(h.dim() == 3 && out.sizes() == h.sizes(), "truss_mi355: h / out must be [B, N, C] of equal shape");
-  const int64_t B = h.size(0), N = h.size(1), C = h.size(2);
+// ---- what the GCN operators share ----
+void check_adj(const at::Tensor &adj, int64_t B, int64_t N) {
   TORCH_CHECK((adj.dim() == 2 || adj.dim() == 3) && adj.size(-1) == N && adj.size(-2) == N && (adj.dim() == 2 || adj.size(0) == B),
               "truss_mi355: adj must be [N, N] or [B, N, N]");
-  const float *pa = ptr<const float>(b, adj, at::kFloat, "adj");
-  const float *ph = ptr<const float>(b, h, at::kFloat, "h");
-  const float *pb = ptr<const float>(b, bias, at::kFloat, "bias", C);
-  float *po = ptr<float>(b, out, at::kFloat, "out");
-  check_rc(b, b.gcn(pa, adj.dim() == 3 ? N * N : 0, ph, pb, po, (int32_t)B, (int32_t)N, (int32_t)C, (int32_t)act, (void *)stream),
-           "truss_gcn_aggregate");
 }
-void gcn_meta(int64_t, int64_t, const at::Tensor &, const at::Tensor &, const OT &, const at::Tensor &, int64_t) {}
-
-// the same over a fixed sparsity pattern (nbr [N, K] int16: the columns that may be non-zero in row i) == truss_gcn_aggregate_sparse
-void gcn_aggregate_sparse(int64_t lib, int64_t stream, const at::Tensor &adj, const at::Tensor &nbr, const at::Tensor &h, const OT &bias,
-                          const at::Tensor &out, int64_t act) {
-  const Backend &b = backend(lib);
-  TORCH_CHECK(b.gcn_sparse, "truss_mi355: the bound native library has no truss_gcn_aggregate_sparse");
-  TORCH_CHECK(h.dim() == 3 && out.sizes() == h.sizes(), "truss_mi355: h / out must be [B, N, C] of equal shape");
-  const int64_t B = h.size(0), N = h.size(1), C = h.size(2);
-  TORCH_CHECK((adj.dim() == 2 || adj.dim() == 3) && adj.size(-1) == N && adj.size(-2) == N && (adj.dim() == 2 || adj.size(0) == B),
-              "truss_mi355: adj must be [N, N] or [B, N, N]");
-  TORCH_CHECK(nbr.dim() == 2 && nbr.size(0) == N, "truss_mi355: nbr must be [N, K]");
-  const float *pa = ptr<const float>(b, adj, at::kFloat, "adj");
-  const int16_t *pn = ptr<const int16_t>(b, nbr, at::kShort, "nbr");
-  const float *ph = ptr<const float>(b, h, at::kFloat, "h");
-  const float *pb = ptr<const float>(b, bias, at::kFloat, "bias", C);
-  float *po = ptr<float>(b, out, at::kFloat, "out");
-  check_rc(b, b.gcn_sparse(pa, adj.dim() == 3 ? N * N : 0, pn, (int32_t)nbr.size(1), ph, pb, po, (int32_t)B, (int32_t)N, (int32_t)C,
-                           (int32_t)act, (void *)stream),
-           "truss_gcn_aggregate_sparse");
-}
-void gcn_sparse_meta(int64_t, int64_t, const at::Tensor &, const at::Tensor &, const at::Tensor &, const OT &, const at::Tensor &, int64_t) {}
-
-// one whole GCN layer, out = act(adj @ (x @ w^T) + bias) [+ out], on the matrix cores == truss_gcn_layer
-void gcn_layer(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
-               const at::Tensor &out, int64_t act, bool accumulate, const OT &w_split) {
-  const Backend &b = backend(lib);
-  TORCH_CHECK(b.gcn_layer, "truss_mi355: the bound native library has no truss_gcn_layer");
-  TORCH_CHECK(x.dim() == 3 && out.dim() == 3 && w.dim() == 2, "truss_mi355: x [B, N, K], w [C, K], out [B, N, C]");
-  const int64_t B = x.size(0), N = x.size(1), K = x.size(2), C = w.size(0);
-  TORCH_CHECK(w.size(1) == K && out.size(0) == B && out.size(1) == N && out.size(2) == C, "truss_mi355: gcn_layer shapes do not match");
-  TORCH_CHECK((adj.dim() == 2 || adj.dim() == 3) && adj.size(-1) == N && adj.size(-2) == N && (adj.dim() == 2 || adj.size(0) == B),
-              "truss_mi355: adj must be [N, N] or [B, N, N]");
+// the argument block of one layer: sizes, activation, x (absent in the backward), the adjacency with its optional sparsity
+// pattern, the weights; bias / out and the rest are the caller's
+truss_gcn_layer_args_t layer_args(const Backend &b, int64_t B, int64_t N, int64_t K, int64_t C, int64_t act, const at::Tensor *x,
+                                  const at::Tensor &adj, const OT &nbr, const at::Tensor &w) {
+  check_adj(adj, B, N);
   truss_gcn_layer_args_t a{};
   a.struct_size = sizeof a;
   a.n_batch = (int32_t)B;
@@ -261,30 +228,77 @@ void gcn_layer(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tenso
   a.k_in = (int32_t)K;
   a.c_out = (int32_t)C;
   a.act = (int32_t)act;
-  a.accumulate = accumulate ? 1 : 0;
-  a.x = ptr<const float>(b, x, at::kFloat, "x");
+  if (x) a.x = ptr<const float>(b, *x, at::kFloat, "x");
   a.adj = ptr<const float>(b, adj, at::kFloat, "adj");
   a.a_batch_stride = adj.dim() == 3 ? N * N : 0;
-  if (nbr.has_value() && nbr->defined()) {
+  if (present(nbr)) {
     TORCH_CHECK(nbr->dim() == 2 && nbr->size(0) == N, "truss_mi355: nbr must be [N, K]");
     a.nbr = ptr<const int16_t>(b, *nbr, at::kShort, "nbr");
     a.k_nbr = (int32_t)nbr->size(1);
   }
   a.w = ptr<const float>(b, w, at::kFloat, "w");
+  return a;
+}
+// the same for a forward layer of operator `op`, from its tensors: shapes checked, bias and out filled in
+truss_gcn_layer_args_t forward_args(const Backend &b, const char *op, const at::Tensor &x, const at::Tensor &adj, const OT &nbr,
+                                    const at::Tensor &w, const OT &bias, const at::Tensor &out, int64_t act) {
+  TORCH_CHECK(x.dim() == 3 && out.dim() == 3 && w.dim() == 2, "truss_mi355: x [B, N, K], w [C, K], out [B, N, C]");
+  const int64_t B = x.size(0), N = x.size(1), K = x.size(2), C = w.size(0);
+  TORCH_CHECK(w.size(1) == K && out.size(0) == B && out.size(1) == N && out.size(2) == C, "truss_mi355: ", op, " shapes do not match");
+  truss_gcn_layer_args_t a = layer_args(b, B, N, K, C, act, &x, adj, nbr, w);
   a.bias = ptr<const float>(b, bias, at::kFloat, "bias", C);
   a.out = ptr<float>(b, out, at::kFloat, "out");
-  a.w_bf16x3 = (const uint16_t *)ptr<const int16_t>(b, w_split, at::kShort, "w_split", 3 * 224 * ((K + 15) / 16 * 16));
+  return a;
+}
+
+// act(A @ H + bias) of a GCN layer for B small graphs (truss2D_RL.py:49-120, inference) == truss_gcn_aggregate
+void gcn_aggregate(int64_t lib, int64_t stream, const at::Tensor &adj, const at::Tensor &h, const OT &bias, const at::Tensor &out,
+                   int64_t act) {
+  const Backend &b = backend(lib);
+  TORCH_CHECK(h.dim() == 3 && out.sizes() == h.sizes(), "truss_mi355: h / out must be [B, N, C] of equal shape");
+  const int64_t B = h.size(0), N = h.size(1), C = h.size(2);
+  check_adj(adj, B, N);
+  const float *pa = ptr<const float>(b, adj, at::kFloat, "adj");
+  const float *ph = ptr<const float>(b, h, at::kFloat, "h");
+  const float *pb = ptr<const float>(b, bias, at::kFloat, "bias", C);
+  float *po = ptr<float>(b, out, at::kFloat, "out");
+  check_rc(b, b.gcn_aggregate(pa, adj.dim() == 3 ? N * N : 0, ph, pb, po, (int32_t)B, (int32_t)N, (int32_t)C, (int32_t)act, (void *)stream),
+           "truss_gcn_aggregate");
+}
+
+// the same over a fixed sparsity pattern (nbr [N, K] int16: the columns that may be non-zero in row i) == truss_gcn_aggregate_sparse
+void gcn_aggregate_sparse(int64_t lib, int64_t stream, const at::Tensor &adj, const at::Tensor &nbr, const at::Tensor &h, const OT &bias,
+                          const at::Tensor &out, int64_t act) {
+  const Backend &b = backend(lib);
+  TORCH_CHECK(h.dim() == 3 && out.sizes() == h.sizes(), "truss_mi355: h / out must be [B, N, C] of equal shape");
+  const int64_t B = h.size(0), N = h.size(1), C = h.size(2);
+  check_adj(adj, B, N);
+  TORCH_CHECK(nbr.dim() == 2 && nbr.size(0) == N, "truss_mi355: nbr must be [N, K]");
+  const float *pa = ptr<const float>(b, adj, at::kFloat, "adj");
+  const int16_t *pn = ptr<const int16_t>(b, nbr, at::kShort, "nbr");
+  const float *ph = ptr<const float>(b, h, at::kFloat, "h");
+  const float *pb = ptr<const float>(b, bias, at::kFloat, "bias", C);
+  float *po = ptr<float>(b, out, at::kFloat, "out");
+  check_rc(b, b.gcn_aggregate_sparse(pa, adj.dim() == 3 ? N * N : 0, pn, (int32_t)nbr.size(1), ph, pb, po, (int32_t)B, (int32_t)N, (int32_t)C,
+                           (int32_t)act, (void *)stream),
+           "truss_gcn_aggregate_sparse");
+}
+
+// one whole GCN layer, out = act(adj @ (x @ w^T) + bias) [+ out], on the matrix cores == truss_gcn_layer
+void gcn_layer(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
+               const at::Tensor &out, int64_t act, bool accumulate, const OT &w_split) {
+  const Backend &b = backend(lib);
+  truss_gcn_layer_args_t a = forward_args(b, "gcn_layer", x, adj, nbr, w, bias, out, act);
+  a.accumulate = accumulate ? 1 : 0;
+  a.w_bf16x3 = (const uint16_t *)ptr<const int16_t>(b, w_split, at::kShort, "w_split", 3 * 224 * ((a.k_in + 15) / 16 * 16));
   check_rc(b, b.gcn_layer(&a, (void *)stream), "truss_gcn_layer");
 }
-void gcn_layer_meta(int64_t, int64_t, const at::Tensor &, const at::Tensor &, const OT &, const at::Tensor &, const OT &, const at::Tensor &,
-                    int64_t, bool, const OT &) {}
 
 // a whole level of GCN layers in one launch: out[i] = act[i](adj[i] @ (x[i] @ w[i]^T) + bias[i]); x_agg (empty, or one tensor per
 // layer) receives adj[i] @ x[i] == truss_gcn_level
 void gcn_level(int64_t lib, int64_t stream, at::TensorList x, at::TensorList adj, const c10::List<OT> &nbr, at::TensorList w, at::TensorList bias,
                at::TensorList out, at::TensorList x_agg, at::IntArrayRef act) {
   const Backend &b = backend(lib);
-  TORCH_CHECK(b.gcn_level, "truss_mi355: the bound native library has no truss_gcn_level");
   const size_t L = x.size();
   TORCH_CHECK(adj.size() == L && w.size() == L && bias.size() == L && out.size() == L && act.size() == L && (x_agg.empty() || x_agg.size() == L) &&
                   (nbr.empty() || nbr.size() == L),
@@ -292,42 +306,14 @@ void gcn_level(int64_t lib, int64_t stream, at::TensorList x, at::TensorList adj
   std::vector<truss_gcn_layer_args_t> args(L);
   std::vector<float *> xa(L, nullptr);
   for (size_t i = 0; i < L; ++i) {
-    TORCH_CHECK(x[i].dim() == 3 && out[i].dim() == 3 && w[i].dim() == 2, "truss_mi355: x [B, N, K], w [C, K], out [B, N, C]");
-    const int64_t B = x[i].size(0), N = x[i].size(1), K = x[i].size(2), C = w[i].size(0);
-    TORCH_CHECK(w[i].size(1) == K && out[i].size(0) == B && out[i].size(1) == N && out[i].size(2) == C, "truss_mi355: gcn_level shapes do not match");
-    TORCH_CHECK((adj[i].dim() == 2 || adj[i].dim() == 3) && adj[i].size(-1) == N && adj[i].size(-2) == N && (adj[i].dim() == 2 || adj[i].size(0) == B),
-                "truss_mi355: adj must be [N, N] or [B, N, N]");
-    truss_gcn_layer_args_t &a = args[i];
-    a = truss_gcn_layer_args_t{};
-    a.struct_size = sizeof a;
-    a.n_batch = (int32_t)B;
-    a.n_nodes = (int32_t)N;
-    a.k_in = (int32_t)K;
-    a.c_out = (int32_t)C;
-    a.act = (int32_t)act[i];
-    a.x = ptr<const float>(b, x[i], at::kFloat, "x");
-    a.adj = ptr<const float>(b, adj[i], at::kFloat, "adj");
-    a.a_batch_stride = adj[i].dim() == 3 ? N * N : 0;
-    if (!nbr.empty()) {
-      const OT pat = nbr.get(i);
-      if (pat.has_value() && pat->defined()) {
-        TORCH_CHECK(pat->dim() == 2 && pat->size(0) == N, "truss_mi355: nbr must be [N, K]");
-        a.nbr = ptr<const int16_t>(b, *pat, at::kShort, "nbr");
-        a.k_nbr = (int32_t)pat->size(1);
-      }
-    }
-    a.w = ptr<const float>(b, w[i], at::kFloat, "w");
-    a.bias = ptr<const float>(b, bias[i], at::kFloat, "bias", C);
-    a.out = ptr<float>(b, out[i], at::kFloat, "out");
+    args[i] = forward_args(b, "gcn_level", x[i], adj[i], at_or_none(nbr, i), w[i], bias[i], out[i], act[i]);
     if (!x_agg.empty()) {
-      TORCH_CHECK(x_agg[i].numel() == B * N * K, "truss_mi355: x_agg[i] must hold B * N * K elements");
+      TORCH_CHECK(x_agg[i].numel() == x[i].numel(), "truss_mi355: x_agg[i] must hold B * N * K elements");
       xa[i] = ptr<float>(b, x_agg[i], at::kFloat, "x_agg");
     }
   }
   check_rc(b, b.gcn_level(args.data(), (int32_t)L, x_agg.empty() ? nullptr : xa.data(), (void *)stream), "truss_gcn_level");
 }
-void gcn_level_meta(int64_t, int64_t, at::TensorList, at::TensorList, const c10::List<OT> &, at::TensorList, at::TensorList, at::TensorList, at::TensorList,
-                    at::IntArrayRef) {}
 
 // the backward of such a level in one launch: d_b[i] = sum_rows dZ, d_w[i] = dZ^T x_agg[i], d_x[i] = adj[i]^T (dZ w[i]) with
 // dZ = d_out[i] * act[i]'(out[i]); the lists of optional tensors are empty or hold one entry per layer (None: not wanted)
@@ -336,7 +322,7 @@ void gcn_level_backward(int64_t lib, int64_t stream, at::TensorList adj, at::Ten
                         at::TensorList out, const c10::List<OT> &x_agg, const c10::List<OT> &d_w, const c10::List<OT> &d_b,
                         const c10::List<OT> &d_x) {
   const Backend &b = backend(lib);
-  TORCH_CHECK(b.gcn_level_bwd, "truss_mi355: the bound native library has no truss_gcn_level_backward");
+  need(b.gcn_level_backward, "truss_gcn_level_backward");
   const size_t L = d_out.size();
   auto per_layer = [L](const c10::List<OT> &l) { return l.empty() || l.size() == L; };
   TORCH_CHECK(adj.size() == L && w.size() == L && act.size() == L && out.size() == L && per_layer(x_agg) && per_layer(d_w) && per_layer(d_b) &&
@@ -344,53 +330,35 @@ void gcn_level_backward(int64_t lib, int64_t stream, at::TensorList adj, at::Ten
               "truss_mi355: gcn_level_backward takes one entry per layer in every list");
   std::vector<truss_gcn_layer_args_t> args(L);
   std::vector<truss_gcn_level_bwd_t> bw(L);
-  auto opt = [](const c10::List<OT> &l, size_t i) -> OT { return l.empty() ? OT() : l.get(i); };
   for (size_t i = 0; i < L; ++i) {
     TORCH_CHECK(d_out[i].dim() == 3 && w[i].dim() == 2 && out[i].sizes() == d_out[i].sizes(),
                 "truss_mi355: d_out / out [B, N, C] of equal shape, w [C, K]");
     const int64_t B = d_out[i].size(0), N = d_out[i].size(1), C = d_out[i].size(2), K = w[i].size(1);
     TORCH_CHECK(w[i].size(0) == C, "truss_mi355: gcn_level_backward shapes do not match");
-    TORCH_CHECK((adj[i].dim() == 2 || adj[i].dim() == 3) && adj[i].size(-1) == N && adj[i].size(-2) == N && (adj[i].dim() == 2 || adj[i].size(0) == B),
-                "truss_mi355: adj must be [N, N] or [B, N, N]");
-    truss_gcn_layer_args_t &a = args[i];
-    a = truss_gcn_layer_args_t{};
-    a.struct_size = sizeof a;
-    a.n_batch = (int32_t)B;
-    a.n_nodes = (int32_t)N;
-    a.k_in = (int32_t)K;
-    a.c_out = (int32_t)C;
-    a.act = (int32_t)act[i];
-    a.adj = ptr<const float>(b, adj[i], at::kFloat, "adj");
-    a.a_batch_stride = adj[i].dim() == 3 ? N * N : 0;
-    a.w = ptr<const float>(b, w[i], at::kFloat, "w");
+    args[i] = layer_args(b, B, N, K, C, act[i], nullptr, adj[i], OT(), w[i]);
     truss_gcn_level_bwd_t &g = bw[i];
-    g = truss_gcn_level_bwd_t{};
     g.d_out = ptr<const float>(b, d_out[i], at::kFloat, "d_out");
     g.out = ptr<const float>(b, out[i], at::kFloat, "out");
-    g.x_agg = ptr<const float>(b, opt(x_agg, i), at::kFloat, "x_agg", B * N * K);
-    const OT dw = opt(d_w, i), db = opt(d_b, i), dx = opt(d_x, i);
-    TORCH_CHECK(!(dw.has_value() && dw->defined()) || dw->numel() == C * K, "truss_mi355: d_w[i] must hold C * K elements");
-    TORCH_CHECK(!(db.has_value() && db->defined()) || db->numel() == C, "truss_mi355: d_b[i] must hold C elements");
-    TORCH_CHECK(!(dx.has_value() && dx->defined()) || dx->numel() == B * N * K, "truss_mi355: d_x[i] must hold B * N * K elements");
+    g.x_agg = ptr<const float>(b, at_or_none(x_agg, i), at::kFloat, "x_agg", B * N * K);
+    const OT dw = at_or_none(d_w, i), db = at_or_none(d_b, i), dx = at_or_none(d_x, i);
+    TORCH_CHECK(!present(dw) || dw->numel() == C * K, "truss_mi355: d_w[i] must hold C * K elements");
+    TORCH_CHECK(!present(db) || db->numel() == C, "truss_mi355: d_b[i] must hold C elements");
+    TORCH_CHECK(!present(dx) || dx->numel() == B * N * K, "truss_mi355: d_x[i] must hold B * N * K elements");
     g.d_w = ptr<float>(b, dw, at::kFloat, "d_w");
     g.d_b = ptr<float>(b, db, at::kFloat, "d_b");
     g.d_x = ptr<float>(b, dx, at::kFloat, "d_x");
   }
-  check_rc(b, b.gcn_level_bwd(args.data(), (int32_t)L, bw.data(), (void *)stream), "truss_gcn_level_backward");
+  check_rc(b, b.gcn_level_backward(args.data(), (int32_t)L, bw.data(), (void *)stream), "truss_gcn_level_backward");
 }
-void gcn_level_backward_meta(int64_t, int64_t, at::TensorList, at::TensorList, at::IntArrayRef, at::TensorList, at::TensorList, const c10::List<OT> &,
-                             const c10::List<OT> &, const c10::List<OT> &, const c10::List<OT> &) {}
 
 // w [C, K] float32 -> out [3, 224, KP] int16 (bfloat16 bit patterns, zero rows / columns beyond C / K): the exact three-term split of the bf16x3 path == truss_gcn_split_w
 void gcn_split_w(int64_t lib, int64_t stream, const at::Tensor &w, const at::Tensor &out) {
   const Backend &b = backend(lib);
-  TORCH_CHECK(b.gcn_split, "truss_mi355: the bound native library has no truss_gcn_split_w");
   TORCH_CHECK(w.dim() == 2 && out.dim() == 3 && out.size(0) == 3 && out.size(1) == 224 && w.size(0) <= 224 && out.size(2) == (w.size(1) + 15) / 16 * 16,
               "truss_mi355: gcn_split_w: w [C <= 224, K], out [3, 224, (K + 15) / 16 * 16]");
-  check_rc(b, b.gcn_split(ptr<const float>(b, w, at::kFloat, "w"), (int32_t)w.size(0), (int32_t)w.size(1),
+  check_rc(b, b.gcn_split_w(ptr<const float>(b, w, at::kFloat, "w"), (int32_t)w.size(0), (int32_t)w.size(1),
                           (uint16_t *)ptr<int16_t>(b, out, at::kShort, "out"), (void *)stream), "truss_gcn_split_w");
 }
-void gcn_split_meta(int64_t, int64_t, const at::Tensor &, const at::Tensor &) {}
 
 // float32 tensor of the bound library's device that need not be contiguous (a view read in place)
 float *view_ptr(const Backend &b, const at::Tensor &t, const char *name) {
@@ -419,7 +387,7 @@ truss_replay_field_t replay_field(const Backend &b, const at::Tensor &ring, cons
   f.ext_row_stride = ext.size(0) > 1 ? ext.stride(0) : 0;
   f.group = (int32_t)group;
   const int64_t row = ring.numel() / capacity;
-  if (nbr.has_value() && nbr->defined()) {
+  if (present(nbr)) {
     TORCH_CHECK(ring.dim() == 3 && nbr->dim() == 2 && nbr->size(0) == ring.size(1) && nbr->size(1) == ring.size(2) && ext.size(1) == ring.size(1) &&
                     ext.size(2) == ring.size(1) && dense_from(ext, 1),
                 "truss_mi355: replay pattern field: ring [capacity, n, k_nbr], nbr [n, k_nbr], outside tensor [rows, n, n] with contiguous matrices");
@@ -448,7 +416,7 @@ truss_replay_field_t replay_field(const Backend &b, const at::Tensor &ring, cons
 void replay_scatter(int64_t lib, int64_t stream, at::TensorList ring, at::TensorList src, const c10::List<OT> &nbr, at::IntArrayRef group,
                     const at::Tensor &rows, int64_t k, int64_t head, int64_t capacity) {
   const Backend &b = backend(lib);
-  TORCH_CHECK(b.replay_scatter, "truss_mi355: the bound native library has no truss_replay_scatter");
+  need(b.replay_scatter, "truss_replay_scatter");
   const size_t F = ring.size();
   TORCH_CHECK(src.size() == F && nbr.size() == F && group.size() == F, "truss_mi355: replay_scatter takes one entry per field in every list");
   TORCH_CHECK(k >= 0 && k <= INT32_MAX && rows.dim() == 2 && rows.size(0) == 4 && rows.size(1) == k, "truss_mi355: rows must be [4, k]");
@@ -457,14 +425,12 @@ void replay_scatter(int64_t lib, int64_t stream, at::TensorList ring, at::Tensor
   const int64_t *pr = ptr<const int64_t>(b, rows, at::kLong, "rows");
   check_rc(b, b.replay_scatter(f.data(), (int32_t)F, pr, (int32_t)k, head, capacity, (void *)stream), "truss_replay_scatter");
 }
-void replay_scatter_meta(int64_t, int64_t, at::TensorList, at::TensorList, const c10::List<OT> &, at::IntArrayRef, const at::Tensor &, int64_t, int64_t,
-                         int64_t) {}
 
 // sample: row r of out[i] <- ring row idx[r] of every field (a pattern field: the whole dense matrix) == truss_replay_gather
 void replay_gather(int64_t lib, int64_t stream, at::TensorList ring, at::TensorList out, const c10::List<OT> &nbr, const at::Tensor &idx,
                    int64_t capacity) {
   const Backend &b = backend(lib);
-  TORCH_CHECK(b.replay_gather, "truss_mi355: the bound native library has no truss_replay_gather");
+  need(b.replay_gather, "truss_replay_gather");
   const size_t F = ring.size();
   TORCH_CHECK(out.size() == F && nbr.size() == F, "truss_mi355: replay_gather takes one entry per field in every list");
   TORCH_CHECK(idx.dim() == 1 && idx.numel() <= INT32_MAX, "truss_mi355: idx must be [batch]");
@@ -477,14 +443,13 @@ void replay_gather(int64_t lib, int64_t stream, at::TensorList ring, at::TensorL
   const int64_t *pi = ptr<const int64_t>(b, idx, at::kLong, "idx");
   check_rc(b, b.replay_gather(f.data(), (int32_t)F, pi, (int32_t)batch, capacity, (void *)stream), "truss_replay_gather");
 }
-void replay_gather_meta(int64_t, int64_t, at::TensorList, at::TensorList, const c10::List<OT> &, const at::Tensor &, int64_t) {}
 
 // the difference reward of K (env, member) pairs in one launch (master_DDPG_truss2D_MO.py:263-368) == truss_reward
 void reward(int64_t lib, int64_t stream, int64_t max_front, const at::Tensor &front_no, const at::Tensor &n_front_no, const at::Tensor &pf_hv,
             const at::Tensor &n_pf_hv, const at::Tensor &parent, const at::Tensor &points, const at::Tensor &ref_points, const at::Tensor &n_pf,
             const at::Tensor &R, const at::Tensor &G_U, const at::Tensor &xmax, const at::Tensor &ymax, const OT &parts) {
   const Backend &b = backend(lib);
-  TORCH_CHECK(b.reward, "truss_mi355: the bound native library has no truss_reward");
+  need(b.reward, "truss_reward");
   TORCH_CHECK(front_no.dim() == 3 && front_no.size(2) == 4, "truss_mi355: front_no must be [K, P, 4]");
   const int64_t K = front_no.size(0), P = front_no.size(1);
   TORCH_CHECK(pf_hv.sizes() == front_no.sizes(), "truss_mi355: pf_hv must be [K, P, 4] like front_no");
@@ -497,7 +462,7 @@ void reward(int64_t lib, int64_t stream, int64_t max_front, const at::Tensor &fr
   TORCH_CHECK(points.dim() == 3 && points.size(0) == K && points.size(1) == 3 && points.size(2) == 4, "truss_mi355: points must be [K, 3, 4]");
   TORCH_CHECK(is2d(R, 3), "truss_mi355: R must be [K, 3]");
   TORCH_CHECK(is1d(G_U) && is1d(xmax) && is1d(ymax), "truss_mi355: G_U / xmax / ymax must be [K]");
-  TORCH_CHECK(!(parts.has_value() && parts->defined()) || is2d(*parts, 8), "truss_mi355: parts must be [K, 8]");
+  TORCH_CHECK(!present(parts) || is2d(*parts, 8), "truss_mi355: parts must be [K, 8]");
   truss_reward_args_t a{};
   a.struct_size = sizeof(truss_reward_args_t);
   a.n_sets = (int32_t)K;
@@ -520,34 +485,45 @@ void reward(int64_t lib, int64_t stream, int64_t max_front, const at::Tensor &fr
   if (K == 0) return;
   check_rc(b, b.reward(&a, (void *)stream), "truss_reward");
 }
-void reward_meta(int64_t, int64_t, int64_t, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &,
-                 const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &, const at::Tensor &,
-                 const at::Tensor &, const OT &) {}
+
+// every operator on meta tensors (tracing): nothing to compute, the schema says what is mutated
+void noop_boxed(const c10::OperatorHandle &op, torch::jit::Stack *s) { torch::jit::drop(*s, op.schema().arguments().size()); }
 
 }  // namespace
 
-// Bind the entry points of a loaded native library (addresses from ctypes) under a small index.
-extern "C" int truss_torch_bind(int lib, void *step_fn, void *rollout_fn, void *obs_fn, void *front_fn, void *gcn_fn, void *gcn_sparse_fn,
-                                void *gcn_layer_fn, void *gcn_split_fn, void *gcn_level_fn, void *gcn_level_bwd_fn, void *replay_scatter_fn,
-                                void *replay_gather_fn, void *reward_fn, void *last_error_fn, int is_device) {
-  if (lib < 0 || lib >= (int)g_backends.size() || !step_fn) return -1;
-  Backend &b = g_backends[lib];
-  b.step = (decltype(b.step))step_fn;
-  b.rollout = (decltype(b.rollout))rollout_fn;
-  b.obs = (decltype(b.obs))obs_fn;
-  b.front = (decltype(b.front))front_fn;
-  b.gcn = (decltype(b.gcn))gcn_fn;
-  b.gcn_sparse = (decltype(b.gcn_sparse))gcn_sparse_fn;
-  b.gcn_layer = (decltype(b.gcn_layer))gcn_layer_fn;
-  b.gcn_split = (decltype(b.gcn_split))gcn_split_fn;
-  b.gcn_level = (decltype(b.gcn_level))gcn_level_fn;
-  b.gcn_level_bwd = (decltype(b.gcn_level_bwd))gcn_level_bwd_fn;   // (may be null: a library without the entry)
-  b.replay_scatter = (decltype(b.replay_scatter))replay_scatter_fn;   // (these two as well)
-  b.replay_gather = (decltype(b.replay_gather))replay_gather_fn;
-  b.reward = (decltype(b.reward))reward_fn;                           // (and this one)
-  b.last_error = (decltype(b.last_error))last_error_fn;
-  b.device = is_device != 0;
+// Bind the entry points of a native library that is already loaded in this process (ctypes did that), looked up by name in the
+// image at `path`, under the small index `lib`.  0, or: -1 `lib` is not an index of the table of libraries, -2 no such image is loaded,
+// -3 the library lacks a required symbol (*missing names it; a missing optional entry just stays null).
+extern "C" int truss_torch_bind(int lib, const char *path, const char **missing) {
+  if (lib < 0 || lib >= (int)g_backends.size()) return -1;
+  void *h = path ? dlopen(path, RTLD_NOW | RTLD_NOLOAD) : nullptr;
+  if (!h) return -2;
+  Backend b;
+  const char *lacks = nullptr;   // the first required symbol the library does not export
+  auto find = [&](const char *symbol, bool required) {
+    void *fn = dlsym(h, symbol);
+    if (!fn && required && !lacks) lacks = symbol;
+    return fn;
+  };
+#define X(field, symbol, required) b.field = (decltype(b.field))find(#symbol, required);
+  TRUSS_ENTRY_POINTS(X)
+#undef X
+  auto backend_name = (decltype(&truss_backend))find("truss_backend", true);
+  dlclose(h);                    // only the reference taken above: the caller keeps the image loaded
+  if (lacks) {
+    if (missing) *missing = lacks;
+    return -3;
+  }
+  b.device = std::strcmp(backend_name(), "hip") == 0;
+  g_backends[lib] = b;
   return 0;
+}
+
+// the symbols of the table, comma-joined (the test-suite holds them against the header)
+extern "C" const char *truss_torch_entries(void) {
+#define X(field, symbol, required) "," #symbol
+  return &(TRUSS_ENTRY_POINTS(X))[1];
+#undef X
 }
 
 #define STEP_SCHEMA_TENSORS                                                                                                          \
@@ -581,48 +557,15 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("reward(int lib, int stream, int max_front, Tensor front_no, Tensor n_front_no, Tensor pf_hv, Tensor n_pf_hv, Tensor parent, Tensor points, "
         "Tensor ref_points, Tensor n_pf, Tensor(a!) R, Tensor(b!) G_U, Tensor(c!) xmax, Tensor(d!) ymax, Tensor(e!)? parts) -> ()");
 }
-TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) {   // the emulator library of the test-suite binds here
-  m.impl("step", step);
-  m.impl("rollout", rollout);
-  m.impl("obs", obs);
-  m.impl("front", front);
-  m.impl("gcn_aggregate", gcn_aggregate);
-  m.impl("gcn_aggregate_sparse", gcn_aggregate_sparse);
-  m.impl("gcn_layer", gcn_layer);
-  m.impl("gcn_split_w", gcn_split_w);
-  m.impl("gcn_level", gcn_level);
-  m.impl("gcn_level_backward", gcn_level_backward);
-  m.impl("replay_scatter", replay_scatter);
-  m.impl("replay_gather", replay_gather);
-  m.impl("reward", reward);
+static void register_operators(torch::Library &m) {
+#define X(field, symbol, required) m.impl(#field, field);
+  TRUSS_OPERATOR_ENTRIES(X)
+#undef X
 }
-TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) {  // = HIP on ROCm: the product library
-  m.impl("step", step);
-  m.impl("rollout", rollout);
-  m.impl("obs", obs);
-  m.impl("front", front);
-  m.impl("gcn_aggregate", gcn_aggregate);
-  m.impl("gcn_aggregate_sparse", gcn_aggregate_sparse);
-  m.impl("gcn_layer", gcn_layer);
-  m.impl("gcn_split_w", gcn_split_w);
-  m.impl("gcn_level", gcn_level);
-  m.impl("gcn_level_backward", gcn_level_backward);
-  m.impl("replay_scatter", replay_scatter);
-  m.impl("replay_gather", replay_gather);
-  m.impl("reward", reward);
-}
-TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {  // tracing: every operator only mutates its outputs
-  m.impl("step", step_meta);
-  m.impl("rollout", rollout_meta);
-  m.impl("obs", obs_meta);
-  m.impl("front", front_meta);
-  m.impl("gcn_aggregate", gcn_meta);
-  m.impl("gcn_aggregate_sparse", gcn_sparse_meta);
-  m.impl("gcn_layer", gcn_layer_meta);
-  m.impl("gcn_split_w", gcn_split_meta);
-  m.impl("gcn_level", gcn_level_meta);
-  m.impl("gcn_level_backward", gcn_level_backward_meta);
-  m.impl("replay_scatter", replay_scatter_meta);
-  m.impl("replay_gather", replay_gather_meta);
-  m.impl("reward", reward_meta);
+TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) { register_operators(m); }    // the emulator library of the test-suite binds here
+TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) { register_operators(m); }   // = HIP on ROCm: the product library
+TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {                            // tracing: every operator only mutates its outputs
+#define X(field, symbol, required) m.impl(#field, torch::CppFunction::makeFromBoxedFunction<&noop_boxed>());
+  TRUSS_OPERATOR_ENTRIES(X)
+#undef X
 }

@@ -70,6 +70,36 @@ class RewardArgs(C.Structure):
 REWARD_MAXP = 61          # truss_reward: P archive rows + 3 new points on one 64-lane wave
 
 
+_i32, _i64 = C.c_int32, C.c_int64
+_STRING_GETTERS = ("truss_last_error", "truss_backend")       # return const char *; every other entry returns int
+# THE table of the C ABI: (symbol, argtypes, optional).  A library may lack the optional entries (the CPU lane emulator does);
+# a missing required one fails the load.  Argument blocks the operators fill (csrc/truss_torch_ops.cpp) are plain pointers here.
+_ENTRIES = [
+    ("truss_abi_version", [], False),
+    ("truss_last_error", [], False),
+    ("truss_backend", [], False),
+    ("truss_topo_create", [C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, C.c_double, _vp], False),
+    ("truss_topo_destroy", [_vp], False),
+    ("truss_topo_dofs", [_vp, _vp, _vp], False),
+    ("truss_topo_solver_info", [_vp, _vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)], False),
+    ("truss_topo_fused_obs", [_vp], False),
+    ("truss_topo_persistent_rollout", [_vp], False),
+    ("truss_step", [_vp, C.POINTER(StepArgs), _vp], False),
+    ("truss_rollout", [_vp, C.POINTER(StepArgs), _i32, _i32, _vp], False),
+    ("truss_obs", [_vp, C.POINTER(ObsArgs), _vp], False),
+    ("truss_front", [C.POINTER(FrontArgs), _vp], False),
+    ("truss_gcn_aggregate", [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], False),
+    ("truss_gcn_aggregate_sparse", [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp], False),
+    ("truss_gcn_layer", [_vp, _vp], False),
+    ("truss_gcn_split_w", [_vp, _i32, _i32, _vp, _vp], False),
+    ("truss_gcn_level", [_vp, _i32, _vp, _vp], False),
+    ("truss_gcn_level_backward", [_vp, _i32, _vp, _vp], True),
+    ("truss_replay_scatter", [_vp, _i32, _vp, _i32, _i64, _i64, _vp], True),
+    ("truss_replay_gather", [_vp, _i32, _vp, _i32, _i64, _vp], True),
+    ("truss_reward", [C.POINTER(RewardArgs), _vp], True),
+]
+
+
 class TrussError(RuntimeError):
     pass
 
@@ -86,55 +116,19 @@ class TrussLib:
         self.path = path
         self.dll = C.CDLL(path)
         d = self.dll
-        d.truss_abi_version.restype = C.c_int
-        d.truss_last_error.restype = C.c_char_p
-        d.truss_backend.restype = C.c_char_p
-        d.truss_topo_create.restype = C.c_int
-        d.truss_topo_create.argtypes = [C.POINTER(_vp), C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp,
-                                        C.c_int32, _vp, C.c_int32, _vp, C.c_double, C.c_double, _vp]
-        d.truss_topo_destroy.argtypes = [_vp]
-        d.truss_topo_dofs.restype = C.c_int
-        d.truss_topo_dofs.argtypes = [_vp, _vp, _vp]
-        d.truss_topo_solver_info.restype = C.c_int
-        d.truss_topo_solver_info.argtypes = [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        d.truss_topo_fused_obs.restype = C.c_int
-        d.truss_topo_fused_obs.argtypes = [_vp]
-        d.truss_topo_persistent_rollout.restype = C.c_int
-        d.truss_topo_persistent_rollout.argtypes = [_vp]
-        d.truss_step.restype = C.c_int
-        d.truss_step.argtypes = [_vp, C.POINTER(StepArgs), _vp]
-        d.truss_rollout.restype = C.c_int
-        d.truss_rollout.argtypes = [_vp, C.POINTER(StepArgs), C.c_int32, C.c_int32, _vp]
-        if hasattr(d, "truss_obs"):
-            d.truss_obs.restype = C.c_int
-            d.truss_obs.argtypes = [_vp, C.POINTER(ObsArgs), _vp]
-        d.truss_gcn_aggregate.restype = C.c_int
-        d.truss_gcn_aggregate.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
-        d.truss_gcn_layer.restype = C.c_int
-        d.truss_gcn_layer.argtypes = [_vp, _vp]
-        d.truss_gcn_level.restype = C.c_int
-        d.truss_gcn_level.argtypes = [_vp, C.c_int32, _vp, _vp]
-        self.has_level_backward = hasattr(d, "truss_gcn_level_backward")     # (optional: the CPU lane emulator does not export it)
-        if self.has_level_backward:
-            d.truss_gcn_level_backward.restype = C.c_int
-            d.truss_gcn_level_backward.argtypes = [_vp, C.c_int32, _vp, _vp]
-        # (optional as well: the replay buffer's fused append / sample)
-        self.has_replay_ops = hasattr(d, "truss_replay_scatter") and hasattr(d, "truss_replay_gather")
-        if self.has_replay_ops:
-            d.truss_replay_scatter.restype = C.c_int
-            d.truss_replay_scatter.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int64, C.c_int64, _vp]   # (truss_replay_field_t *: filled by the operators)
-            d.truss_replay_gather.restype = C.c_int
-            d.truss_replay_gather.argtypes = [_vp, C.c_int32, _vp, C.c_int32, C.c_int64, _vp]
-        self.has_reward = hasattr(d, "truss_reward")                         # (optional: the difference reward as one launch)
-        if self.has_reward:
-            d.truss_reward.restype = C.c_int
-            d.truss_reward.argtypes = [C.POINTER(RewardArgs), _vp]
-        d.truss_gcn_split_w.restype = C.c_int
-        d.truss_gcn_split_w.argtypes = [_vp, C.c_int32, C.c_int32, _vp, _vp]
-        d.truss_gcn_aggregate_sparse.restype = C.c_int
-        d.truss_gcn_aggregate_sparse.argtypes = [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]
-        d.truss_front.restype = C.c_int
-        d.truss_front.argtypes = [C.POINTER(FrontArgs), _vp]
+        found = set()
+        for name, argtypes, _ in _ENTRIES:
+            fn = getattr(d, name, None)
+            if fn is not None:
+                fn.restype = C.c_char_p if name in _STRING_GETTERS else C.c_int
+                fn.argtypes = argtypes
+                found.add(name)
+        missing = [name for name, _, optional in _ENTRIES if not optional and name not in found]
+        if missing:
+            raise TrussError(f"{path} does not export {', '.join(missing)}: not a build of include/truss_mi355.h")
+        self.has_level_backward = "truss_gcn_level_backward" in found
+        self.has_replay_ops = {"truss_replay_scatter", "truss_replay_gather"} <= found      # the replay buffer's fused append / sample
+        self.has_reward = "truss_reward" in found
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")
         self.backend = d.truss_backend().decode()

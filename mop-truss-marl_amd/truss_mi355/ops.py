@@ -1,11 +1,11 @@
 """torch.ops.truss_mi355.* -- the env step as PyTorch custom operators.
 
-`csrc/truss_torch_ops.cpp` registers `step`, `rollout`, `obs`, `front`, `gcn_aggregate`, `gcn_aggregate_sparse`, `gcn_layer`, `gcn_level`, `gcn_level_backward`, `replay_scatter`, `replay_gather` and `reward` with the dispatcher
-(CPU / CUDA(=HIP) / Meta keys): tensors in, outputs mutated in place, launched on the stream the caller names,
+`csrc/truss_torch_ops.cpp` registers one operator per native entry point of its table (`entries()` lists them) with the
+dispatcher (CPU / CUDA(=HIP) / Meta keys): tensors in, outputs mutated in place, launched on the stream the caller names,
 capturable in a hipGraph, traceable.  The operators do no arithmetic; they call the C ABI of the native library that
-`bind()` registered under an index -- the HIP product library, or (test-suite only) the CPU lane emulator.  Entry points a
-library may lack (`truss_gcn_level_backward`, the replay pair, `truss_reward`) are bound as null; their operators then fail
-with "the bound native library has no ...".
+`bind()` registered under an index -- the HIP product library, or (test-suite only) the CPU lane emulator.  `bind()` hands
+over the library's path; the entry points are looked up by name there.  A library without a required one is refused, the
+optional ones (`_lib._ENTRIES`) stay null and their operators then fail with "the bound native library has no ...".
 
 There is no fallback: without `libtruss_torch_ops.so` (built by `make -C mop-truss-marl_amd/csrc`) loading fails.
 """
@@ -32,27 +32,25 @@ def _load():
         torch.ops.load_library(OPS_LIB)              # runs the TORCH_LIBRARY registrations
         _dll = C.CDLL(OPS_LIB)                       # the same image: for truss_torch_bind
         _dll.truss_torch_bind.restype = C.c_int
-        _dll.truss_torch_bind.argtypes = [C.c_int] + [C.c_void_p] * 14 + [C.c_int]
+        _dll.truss_torch_bind.argtypes = [C.c_int, C.c_char_p, C.POINTER(C.c_char_p)]
+        _dll.truss_torch_entries.restype = C.c_char_p
     return _dll
+
+
+def entries() -> list:
+    """Symbols of the native entry points the operators call (the table of csrc/truss_torch_ops.cpp)."""
+    return _load().truss_torch_entries().decode().split(",")
 
 
 def bind(lib: "_lib.TrussLib") -> int:
     """Index under which the operators reach this native library's entry points."""
     if lib.path not in _ids:
-        dll, idx = _load(), len(_ids)
-        d = lib.dll
-        addr = lambda f: C.cast(f, C.c_void_p)
-        rc = dll.truss_torch_bind(idx, addr(d.truss_step), addr(d.truss_rollout), addr(d.truss_obs), addr(d.truss_front),
-                                  addr(d.truss_gcn_aggregate), addr(d.truss_gcn_aggregate_sparse), addr(d.truss_gcn_layer),
-                                  addr(d.truss_gcn_split_w), addr(d.truss_gcn_level),
-                                  addr(d.truss_gcn_level_backward) if lib.has_level_backward else None,   # (the emulator has none)
-                                  addr(d.truss_replay_scatter) if lib.has_replay_ops else None,
-                                  addr(d.truss_replay_gather) if lib.has_replay_ops else None,
-                                  addr(d.truss_reward) if lib.has_reward else None,
-                                  addr(d.truss_last_error),
-                                  1 if lib.backend == "hip" else 0)
+        idx, missing = len(_ids), C.c_char_p()
+        rc = _load().truss_torch_bind(idx, os.fsencode(lib.path), C.byref(missing))
         if rc != 0:
-            raise _lib.TrussError("truss_torch_bind failed (more than 8 native libraries bound?)")
+            why = {-1: "more than 8 native libraries bound?", -2: "the library is not loaded in this process"}.get(rc) \
+                or f"the library does not export {missing.value.decode()}"
+            raise _lib.TrussError(f"truss_torch_bind({lib.path}) failed: {why}")
         _ids[lib.path] = idx
     return _ids[lib.path]
 

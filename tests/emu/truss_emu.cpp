@@ -410,25 +410,18 @@ static inline float emu_bf16_top(float x) {
   return x;
 }
 
-// truss_gcn_layer, CPU stand-in of the MFMA kernel (plain loops, the same operation order: aggregate the input rows, then the
-// product with W^T, then bias / activation / accumulation) -- lets the host-side plumbing of the actors run in the CPU tests.
+// ---- truss_gcn_layer / truss_gcn_level: plain loops behind the argument checks the HIP entries use ----
+#include "../../mop-truss-marl_amd/csrc/truss_gcn.h"
+// One layer, CPU stand-in of the MFMA kernel (the same operation order: aggregate the input rows, then the product with W^T, then
+// bias / activation / accumulation) -- lets the host-side plumbing of the actors run in the CPU tests.
 // With split weights (w_bf16x3) it does what the bf16x3 kernel does: the weights come from the [3][224][kp] image (not from w),
 // every aggregated input value is split into three truncated bfloat16 terms (tg_split_term), and the six partial products
-// a0 b0 + a0 b1 + a1 b0 + a0 b2 + a1 b1 + a2 b0 are summed in float32; same envelope as the kernel
-extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *) {
-  if (!a || a->struct_size != sizeof(truss_gcn_layer_args_t)) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: bad argument block");
-  if (!a->x || !a->adj || !a->w || !a->out) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: a required pointer is NULL");
-  if (a->c_out > 224 || a->n_nodes > 256 || (a->nbr ? (a->k_nbr < 1 || a->k_nbr > 16) : a->n_nodes > 64))
-    return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: shape outside the kernel's envelope");
+// a0 b0 + a0 b1 + a1 b0 + a0 b2 + a1 b1 + a2 b0 are summed in float32
+static void emu_gcn_layer(const truss_gcn_layer_args_t *a) {
   const int N = a->n_nodes, K = a->k_in, C = a->c_out;
   const long xs = a->x_row_stride ? a->x_row_stride : K, os = a->out_row_stride ? a->out_row_stride : C;
   const uint16_t *ws = a->w_bf16x3;
   const int KP = (K + 15) & ~15;
-  if (ws) {
-    const int kn = a->nbr ? a->k_nbr : N;
-    if (C <= 32 || K % 4 != 0 || xs % 4 != 0 || ((size_t)a->x & 15) != 0 || kn > 9 || ((size_t)ws & 15) != 0)
-      return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: the bf16x3 path takes c_out 33..224, k_in % 4 == 0, 16-byte aligned x / split weights, <= 9 terms per row");
-  }
   auto wterm = [&](int t, int c, int k) {
     uint32_t u = (uint32_t)ws[((size_t)t * 224 + c) * KP + k] << 16;
     float f;
@@ -477,19 +470,27 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *) {
         *o = a->accumulate ? *o + acc : acc;
       }
   }
+}
+
+extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *) {
+  if (!a) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: NULL argument");
+  if (int rc = tb_gcn_layer_check(a, "truss_gcn_layer", 256, 0, false)) return rc;
+  if (a->n_batch == 0) return TRUSS_OK;
+  if (a->w_bf16x3)
+    if (int rc = tb_gcn_bf16x3_check(a)) return rc;
+  emu_gcn_layer(a);
   return TRUSS_OK;
 }
 
 // truss_gcn_level, CPU stand-in: the layers one after the other through the stand-in above, X' = A X stored where asked for
-extern "C" int truss_gcn_level(const truss_gcn_layer_args_t *layers, int32_t n_layers, float *const *x_agg, void *st) {
+extern "C" int truss_gcn_level(const truss_gcn_layer_args_t *layers, int32_t n_layers, float *const *x_agg, void *) {
   if (n_layers < 0 || (n_layers > 0 && !layers)) return tb_fail(TRUSS_EINVAL, "truss_gcn_level: bad argument");
+  for (int l = 0; l < n_layers; ++l)          // (all layers are checked before any is written, as on the GPU)
+    if (int rc = tb_gcn_layer_check(layers + l, "truss_gcn_level", 128, TG_LEVEL_MAX_K_IN, true)) return rc;
   for (int l = 0; l < n_layers; ++l) {
     const truss_gcn_layer_args_t *a = layers + l;
-    if (a->struct_size != sizeof(truss_gcn_layer_args_t)) return tb_fail(TRUSS_EINVAL, "truss_gcn_level: bad argument block");
     if (a->n_batch == 0) continue;
-    if (a->accumulate || a->w_bf16x3 || a->n_nodes > 128 || a->k_in > 256)
-      return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_level: shape / mode outside the kernel's envelope");
-    if (int rc = truss_gcn_layer(a, st)) return rc;
+    emu_gcn_layer(a);
     if (!x_agg || !x_agg[l]) continue;
     const int N = a->n_nodes, K = a->k_in;
     const long xs = a->x_row_stride ? a->x_row_stride : K;

@@ -23,7 +23,7 @@ def build_emu(mutants=False):
     out = EMU_MUTANT_LIB if mutants else EMU_LIB
     csrc = os.path.join(ROOT, "mop-truss-marl_amd", "csrc")     # every csrc header truss_emu.cpp includes
     deps = [src, os.path.join(ROOT, "include", "truss_mi355.h")] + [
-        os.path.join(csrc, h) for h in ("truss_body.h", "truss_host.h", "truss_front.h", "truss_gcn_aggregate.h")]
+        os.path.join(csrc, h) for h in ("truss_body.h", "truss_host.h", "truss_front.h", "truss_gcn_aggregate.h", "truss_gcn.h")]
     if (not os.path.exists(out)) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         # TRUSS_EMU_CXXFLAGS: e.g. -DTRUSS_PIPELINE=1 to emulate the alternative factorisation schedule
         extra = os.environ.get("TRUSS_EMU_CXXFLAGS", "").split() + (["-DTRUSS_EMU_MUTANTS"] if mutants else [])

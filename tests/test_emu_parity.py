@@ -3,13 +3,15 @@ and of the C ABI surface.  No GPU needed."""
 import ctypes
 import os
 import re
+import subprocess
+import types
 
 import numpy as np
 import pytest
 import torch
 
 import truss_mi355 as tm
-from truss_mi355 import synthetic
+from truss_mi355 import ops, synthetic
 from oracle import truss_oracle as O
 from conftest import ROOT, SCENARIOS
 import parity_common as pc
@@ -208,6 +210,25 @@ def test_product_refuses_non_hip_default(monkeypatch, tmp_path):
     missing = tmp_path / "nope.so"
     with pytest.raises(tm.TrussError):
         tm._lib.TrussLib(str(missing))
+
+
+def test_missing_required_symbol_is_named(tmp_path):
+    """A library without a required entry point is refused when it is loaded, by the name of what it lacks (an optional one may
+    be missing: the emulator loads)."""
+    src = tmp_path / "stub.c"
+    src.write_text('int truss_abi_version(void) { return 3; }\n'
+                   'const char *truss_backend(void) { return "stub"; }\n'
+                   'const char *truss_last_error(void) { return ""; }\n'
+                   'int truss_step(const void *t, const void *a, void *s) { return 0; }\n')
+    stub = tmp_path / "libtruss_stub.so"
+    subprocess.check_call(["g++", "-x", "c", "-fPIC", "-shared", "-o", str(stub), str(src)])
+    with pytest.raises(tm.TrussError, match="truss_rollout") as e:
+        tm._lib.TrussLib(str(stub))
+    for name, _, optional in tm._lib._ENTRIES:
+        assert (name in str(e.value)) == (not optional and name not in ("truss_abi_version", "truss_backend", "truss_last_error", "truss_step")), name
+    ctypes.CDLL(str(stub))                       # loaded behind TrussLib's back: the operator library refuses it by name as well
+    with pytest.raises(tm.TrussError, match="does not export truss_rollout"):
+        ops.bind(types.SimpleNamespace(path=str(stub)))
 
 
 def test_hip_kernels_use_no_scratch():

@@ -7,6 +7,7 @@ must violate it in the same test.
 The taus (gcn_reference.TAU) sit at least 2x above the largest max |got - ref64| / Mag measured on an MI355X over these tests;
 the values are recorded next to each tau."""
 import copy
+import ctypes
 
 import numpy as np
 import pytest
@@ -160,6 +161,46 @@ def test_gcn_layer_envelope_emulated(monkeypatch):
 @pytest.mark.gpu
 def test_gcn_layer_envelope_hip(monkeypatch):
     _check_gcn_layer_envelope(tm.load(), "cuda", monkeypatch)
+
+
+class _LayerArgs(ctypes.Structure):          # truss_gcn_layer_args_t (include/truss_mi355.h)
+    _fields_ = [("struct_size", ctypes.c_size_t)] + [(n, ctypes.c_int32) for n in ("n_batch", "n_nodes", "k_in", "c_out", "act", "accumulate", "k_nbr", "reserved")] + \
+               [("x", ctypes.c_void_p), ("x_row_stride", ctypes.c_int64), ("adj", ctypes.c_void_p), ("a_batch_stride", ctypes.c_int64),
+                ("nbr", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("out_row_stride", ctypes.c_int64), ("w_bf16x3", ctypes.c_void_p)]
+
+
+def _check_gcn_refusals(lib, device):
+    """What truss_gcn_layer / truss_gcn_level refuse is one piece of host code for the product and the emulator: an activation
+    code of 3, out aliasing x, and a level with a layer that accumulates -- same code, same text, nothing launched or written."""
+    B, N, K, C = 1, 2, 4, 4
+    x, adj, w, b = (torch.ones(*s, device=device) for s in ((B, N, K), (N, N), (C, K), (C,)))
+    ns, lid, st = ops.namespace(), ops.bind(lib), ops.stream_of(x.device)
+    out = torch.full((B, N, C), 7.0, device=device)
+    with pytest.raises(tm.TrussError, match=r"truss_gcn_layer failed \(-1\): truss_gcn_layer: bad sizes / act"):
+        ops.call(ns.gcn_layer, lid, st, x, adj, None, w, b, out, 3, False, None)
+    with pytest.raises(tm.TrussError, match=r"truss_gcn_layer failed \(-1\): truss_gcn_layer: out must not alias x"):
+        ops.call(ns.gcn_layer, lid, st, x, adj, None, w, b, x, 0, False, None)
+    with pytest.raises(tm.TrussError, match=r"truss_gcn_level failed \(-1\): truss_gcn_level: out must not alias x"):
+        ops.call(ns.gcn_level, lid, st, [x, x], [adj, adj], [], [w, w], [b, b], [out, x], [], [0, 0])
+    outs = [torch.full((B, N, C), 7.0, device=device) for _ in range(2)]
+    layers = (_LayerArgs * 2)(*[_LayerArgs(struct_size=ctypes.sizeof(_LayerArgs), n_batch=B, n_nodes=N, k_in=K, c_out=C, act=1, accumulate=i,
+                                           x=x.data_ptr(), adj=adj.data_ptr(), w=w.data_ptr(), bias=b.data_ptr(), out=o.data_ptr())
+                                for i, o in enumerate(outs)])
+    with pytest.raises(tm.TrussError, match=r"failed \(-2\): truss_gcn_level: float32 product, no accumulation into out"):
+        lib.check(lib.dll.truss_gcn_level(layers, 2, None, st), "truss_gcn_level")
+    if device == "cuda":
+        torch.cuda.synchronize()
+    assert torch.equal(x, torch.ones_like(x)) and all(torch.equal(o, torch.full_like(o, 7.0)) for o in [out] + outs)
+
+
+def test_gcn_refusals_emulated():
+    _check_gcn_refusals(pc.emu_lib(), "cpu")
+
+
+@pytest.mark.gpu
+def test_gcn_refusals_hip():
+    _check_gcn_refusals(tm.load(), "cuda")
 
 
 def _check_sigmoid_saturation(lib, device):

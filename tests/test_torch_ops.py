@@ -1,12 +1,15 @@
 """The PyTorch custom-operator boundary (torch.ops.truss_mi355.*, csrc/truss_torch_ops.cpp): registration, schemas,
 argument checks, Meta kernels (CPU, through the lane emulator), and -- on the GPU -- hipGraph capture of the fused
 step."""
+import os
+import re
+
 import numpy as np
 import pytest
 import torch
 
 import truss_mi355 as tm
-from truss_mi355 import ops, synthetic
+from truss_mi355 import _lib, ops, synthetic
 import parity_common as pc
 
 
@@ -73,6 +76,40 @@ def test_meta_kernels_make_the_operators_traceable():
             m(B, E, dt=torch.uint8), m(B, 4), None, None, None, None, None, None, m(B, N, 13), None, None, None, None, None)
     ns.gcn_aggregate(0, 0, m(N, N), m(B, N, 16), m(16), m(B, N, 16), 1)
     ns.front(0, 0, 20, 1, m(B, 8, 4, dt=torch.float64), m(B, dt=torch.int32), None, None, None, None, None, None)
+
+
+def test_entry_table_matches_the_header():
+    """The operator library binds by name what its table lists; the table is the header: every function of include/truss_mi355.h
+    that takes a `void *stream`, and truss_last_error.  A new entry point without a table line fails here."""
+    with open(os.path.join(pc.ROOT, "include", "truss_mi355.h")) as f:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", "", f.read(), flags=re.S)
+    launched = {name for name, params in re.findall(r"\b(truss_\w+)\s*\(([^;{}()]*)\)\s*;", text) if re.search(r"void\s*\*\s*stream\b", params)}
+    assert len(launched) >= 13 and "truss_step" in launched and "truss_reward" in launched
+    entries = ops.entries()
+    assert len(entries) == len(set(entries))
+    assert set(entries) == launched | {"truss_last_error"}
+
+
+def test_operators_of_entries_the_library_lacks_name_their_own_symbol():
+    """Entry points are bound by name, so an operator can only ever reach its own: on the lane emulator, which exports none of the
+    optional entries, each of their operators refuses with the name of its own symbol."""
+    lib = pc.emu_lib()
+    assert not (lib.has_level_backward or lib.has_replay_ops or lib.has_reward)
+    ns, lid = ops.namespace(), ops.bind(lib)
+    t = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt)
+    f64, i32 = torch.float64, torch.int32
+    calls = {
+        "truss_gcn_level_backward": (ns.gcn_level_backward, [t(4, 4)], [t(3, 5)], [1], [t(2, 4, 3)], [t(2, 4, 3)], [t(8, 5)], [t(3, 5)], [None], []),
+        "truss_replay_scatter": (ns.replay_scatter, [t(8, 3)], [t(2, 3)], [None], [0], t(4, 2, dt=torch.int64), 2, 0, 8),
+        "truss_replay_gather": (ns.replay_gather, [t(8, 3)], [t(2, 3)], [None], t(2, dt=torch.int64), 8),
+        "truss_reward": (ns.reward, 20, t(2, 5, 4, dt=f64), t(2, dt=i32), t(2, 5, 4, dt=f64), t(2, dt=i32), t(2, 2, dt=f64), t(2, 3, 4, dt=f64),
+                         t(2, 2, dt=f64), t(2, dt=i32), t(2, 3, dt=f64), t(2, dt=f64), t(2, dt=f64), t(2, dt=f64), None),
+    }
+    optional = {name for name, _, opt in _lib._ENTRIES if opt}
+    assert set(calls) == optional and optional < set(ops.entries())
+    for symbol, (op, *args) in calls.items():
+        with pytest.raises(tm.TrussError, match=rf"has no {symbol}$"):
+            ops.call(op, lid, 0, *args)
 
 
 @pytest.mark.gpu
