@@ -1,6 +1,6 @@
-// truss_host.h -- host side of the C ABI (include/truss_mi355.h): topology tables, DOF numbering,
-// band ordering, LDS layout, argument checking and kernel selection.  Header-only and backend
-// agnostic: the includer provides
+// truss_host.h -- host side of the C ABI (include/truss_mi355.h).  truss_topo_create is a sequence of phases, one function each:
+// tb_check_args, tb_dof_numbering, tb_vertical_pairs, tb_node_ordering, tb_pick_variant, TbGeometry (teams, band offsets),
+// tb_build_tables (the blob), tb_lds_layout, tb_build_emit; truss_topo owns its device memory.  Header-only; the includer provides
 //     TRUSS_BACKEND_NAME                           "hip" | "emu"
 //     void *tb_dev_alloc(size_t);  void tb_dev_free(void *);
 //     bool tb_dev_upload(void *dst, const void *src, size_t bytes);
@@ -9,13 +9,13 @@
 //     int  tb_launch_obs(const truss_topo *, const ObsArgsDev &, void *stream);
 //     int  tb_launch_rollout(const truss_topo *, const StepArgsDev &, int n_steps, int n_sets, void *stream);
 //          (all chained steps in one launch; only asked for when tb_rollout_one_launch() says the topology allows it)
-// truss_hip.hip implements them with the HIP runtime; tests/emu/truss_emu.cpp with malloc and the
-// CPU lane emulator.
+// truss_hip.hip implements them with the HIP runtime; tests/emu/truss_emu.cpp with malloc and the CPU lane emulator.
 #pragma once
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <queue>
 #include <string>
 #include <vector>
@@ -110,13 +110,13 @@ static inline size_t tb_obs_lds_bytes(int N) {
   return ((((size_t)(N * 13 + 26 + 128) * 4 + 15) & ~(size_t)15) + (size_t)3 * tb_obs_tile_rows(N) * N * 4 + 15) & ~(size_t)15;
 }
 
-
+// appends a table to a blob, 16-byte aligned; returns its byte offset (a TopoDev f_* / et_* field)
 template <typename T>
-static size_t tb_push(std::vector<char> &blob, const std::vector<T> &v) {
+static int32_t tb_push(std::vector<char> &blob, const std::vector<T> &v) {
   size_t off = (blob.size() + 15) & ~size_t(15);
   blob.resize(off + std::max<size_t>(v.size(), 1) * sizeof(T));
   if (!v.empty()) memcpy(blob.data() + off, v.data(), v.size() * sizeof(T));
-  return off;
+  return (int32_t)off;
 }
 
 struct truss_topo {
@@ -126,10 +126,17 @@ struct truss_topo {
   TopoDev dev{};        // what a plain step launch gets
   TopoDev dev_emit{};   // ... an EMIT launch: the staged tables include the nN_x_e gather table (larger blob_bytes / o_env0)
   size_t lds_bytes_emit = 0;
-  void *blob = nullptr;
-  void *etab = nullptr;   // emission tables of the fused observation writer (TopoDev::etab)
+  void *blob = nullptr;   // device memory, owned: the topology tables (TopoDev::blob) ...
+  void *etab = nullptr;   // ... and the emission tables of the fused observation writer (TopoDev::etab)
   size_t lds_bytes = 0;
   int n_sections = 0;
+  truss_topo() = default;
+  truss_topo(const truss_topo &) = delete;
+  truss_topo &operator=(const truss_topo &) = delete;
+  ~truss_topo() {
+    if (blob) tb_dev_free(blob);
+    if (etab) tb_dev_free(etab);
+  }
 };
 
 // ---- fused observation emission: feature bank placement + gather tables (TopoDev "emit" fields) -------------
@@ -241,32 +248,33 @@ static bool tb_build_emit(truss_topo *t, const int32_t *conn, const uint8_t *res
     return out;
   };
   std::vector<char> tab;
-  D.et_xn = (int32_t)tb_push(tab, paired(txn, IX));
-  D.et_nxn = (int32_t)tb_push(tab, paired(tnxn, IN_));
-  D.et_mat = (int32_t)tb_push(tab, paired(tmat, IM));
+  D.et_xn = tb_push(tab, paired(txn, IX));
+  D.et_nxn = tb_push(tab, paired(tnxn, IN_));
+  D.et_mat = tb_push(tab, paired(tmat, IM));
   tab.resize((tab.size() + 15) & ~size_t(15));
-  t->etab = tb_dev_alloc(tab.size());
-  if (!t->etab || !tb_dev_upload(t->etab, tab.data(), tab.size())) {
-    if (t->etab) tb_dev_free(t->etab);
-    t->etab = nullptr;
-    return false;
-  }
+  t->etab = tb_dev_alloc(tab.size());   // t's from here on, whatever becomes of the upload
+  if (!t->etab || !tb_dev_upload(t->etab, tab.data(), tab.size())) return false;
   D.etab = (const char *)t->etab;
-  D.f_tnxe = (int32_t)tb_push(blob, D.nxe_cw == 4 ? padded(tnxe, IE) : tnxe);   // LDS-resident, staged by EMIT launches only
+  D.f_tnxe = tb_push(blob, D.nxe_cw == 4 ? padded(tnxe, IE) : tnxe);   // LDS-resident, staged by EMIT launches only
   blob.resize((blob.size() + 15) & ~size_t(15));
   D.emit_ok = 1;
   return true;
 }
 
-// --- DOF numbering, FEM_2Dtruss.py:227-261 ---------------------------------------------------
-static void tb_dof_numbering(const uint8_t *res, int N, std::vector<int32_t> &nsc, int &ndof) {
-  nsc.assign(2 * N, 0);
+// --- DOF numbering, FEM_2Dtruss.py:227-261 (nsc: free DOFs first), and every element's four DOFs, :311-317 (ttnsc) ---
+static void tb_dof_numbering(truss_topo &t, const int32_t *conn, const uint8_t *res) {
+  const int N = t.N;
+  t.nsc.assign(2 * N, 0);
   int c = 1;
   for (int i = 0; i < 2 * N; ++i)
-    if (res[i] == 0) nsc[i] = c++;
-  ndof = c - 1;
+    if (res[i] == 0) t.nsc[i] = c++;
+  t.ndof = c - 1;
   for (int i = 0; i < 2 * N; ++i)
-    if (res[i] != 0) nsc[i] = c++;
+    if (res[i] != 0) t.nsc[i] = c++;
+  t.n_rest = 2 * N - t.ndof;
+  t.ttnsc.resize(4 * t.E);
+  for (int e = 0; e < t.E; ++e)
+    for (int q = 0; q < 4; ++q) t.ttnsc[4 * e + q] = t.nsc[2 * conn[2 * e + (q >> 1)] + (q & 1)];
 }
 
 // half bandwidth (in DOFs) of K when nodes are visited in `order`
@@ -329,107 +337,100 @@ extern "C" int truss_abi_version(void) { return TRUSS_ABI_VERSION; }
 extern "C" const char *truss_last_error(void) { return g_truss_err.c_str(); }
 extern "C" const char *truss_backend(void) { return TRUSS_BACKEND_NAME; }
 
-extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const int32_t *conn, const uint8_t *res,
-                                 const uint8_t *top, const int32_t *pair, const uint8_t *load_mask,
-                                 int32_t n_sym_nodes, const int32_t *sym_nodes, int32_t n_sym_elems,
-                                 const int32_t *sym_elems, int32_t n_sections, const double *sections, double e_mod,
-                                 double long_stress, const int32_t *node_order) {
-  if (!out || !conn || !res || !top || !sections) return tb_fail(TRUSS_EINVAL, "NULL argument");
+// ================= truss_topo_create: the phases, in the order they run =================
+// what the caller passed (the arguments of truss_topo_create behind `out`, in their order)
+struct TbInput {
+  int N, E;
+  const int32_t *conn;
+  const uint8_t *res, *top;
+  const int32_t *pair;
+  const uint8_t *load_mask;
+  int n_sym_nodes;
+  const int32_t *sym_nodes;
+  int n_sym_elems;
+  const int32_t *sym_elems;
+  int n_sections;
+  const double *sections;
+  double e_mod, long_stress;
+  const int32_t *node_order;
+};
+
+// ---- argument checks ----
+static int tb_check_args(truss_topo_t **out, const TbInput &in) {
+  const int N = in.N, E = in.E;
+  const int32_t *conn = in.conn;
+  if (!out || !conn || !in.res || !in.top || !in.sections) return tb_fail(TRUSS_EINVAL, "NULL argument");
   if (N < 2 || E < 1 || N > 16000) return tb_fail(TRUSS_EINVAL, "bad N/E");
-  if (n_sections < 1) return tb_fail(TRUSS_EINVAL, "need at least one section");
-  if ((n_sym_nodes > 0 && !sym_nodes) || (n_sym_elems > 0 && !sym_elems)) return tb_fail(TRUSS_EINVAL, "sym table NULL");
+  if (in.n_sections < 1) return tb_fail(TRUSS_EINVAL, "need at least one section");
+  if ((in.n_sym_nodes > 0 && !in.sym_nodes) || (in.n_sym_elems > 0 && !in.sym_elems)) return tb_fail(TRUSS_EINVAL, "sym table NULL");
   for (int e = 0; e < E; ++e)
     if (conn[2 * e] < 0 || conn[2 * e] >= N || conn[2 * e + 1] < 0 || conn[2 * e + 1] >= N || conn[2 * e] == conn[2 * e + 1])
       return tb_fail(TRUSS_EINVAL, "conn out of range");
-  for (int i = 0; i < n_sym_nodes * 2; ++i)
-    if (sym_nodes[i] < 0 || sym_nodes[i] >= N) return tb_fail(TRUSS_EINVAL, "sym_nodes out of range");
-  for (int i = 0; i < n_sym_elems * 2; ++i)
-    if (sym_elems[i] < 0 || sym_elems[i] >= E) return tb_fail(TRUSS_EINVAL, "sym_elems out of range");
-
+  for (int i = 0; i < in.n_sym_nodes * 2; ++i)
+    if (in.sym_nodes[i] < 0 || in.sym_nodes[i] >= N) return tb_fail(TRUSS_EINVAL, "sym_nodes out of range");
+  for (int i = 0; i < in.n_sym_elems * 2; ++i)
+    if (in.sym_elems[i] < 0 || in.sym_elems[i] >= E) return tb_fail(TRUSS_EINVAL, "sym_elems out of range");
   for (int e = 0; e < E; ++e)
     for (int f = e + 1; f < E; ++f)
       if ((conn[2 * e] == conn[2 * f] && conn[2 * e + 1] == conn[2 * f + 1]) ||
           (conn[2 * e] == conn[2 * f + 1] && conn[2 * e + 1] == conn[2 * f]))
         return tb_fail(TRUSS_EUNSUPPORTED, "two elements join the same pair of nodes (parallel members are not supported)");
-  truss_topo *t = new truss_topo();
-  t->N = N;
-  t->E = E;
-  t->n_sections = n_sections;
-  tb_dof_numbering(res, N, t->nsc, t->ndof);
-  if (t->ndof < 1) {
-    delete t;
-    return tb_fail(TRUSS_EINVAL, "no free DOF");
-  }
-  t->n_rest = 2 * N - t->ndof;
-  t->ttnsc.resize(4 * E);
-  for (int e = 0; e < E; ++e) {  // FEM_2Dtruss.py:311-317
-    int a = conn[2 * e], b = conn[2 * e + 1];
-    t->ttnsc[4 * e + 0] = t->nsc[2 * a];
-    t->ttnsc[4 * e + 1] = t->nsc[2 * a + 1];
-    t->ttnsc[4 * e + 2] = t->nsc[2 * b];
-    t->ttnsc[4 * e + 3] = t->nsc[2 * b + 1];
-  }
-  // vertical pairs
-  std::vector<int16_t> pairs;
-  if (pair) {
-    for (int i = 0; i < N; ++i) {
-      int j = pair[i];
-      if (j < 0 || j >= N || j == i || pair[j] != i) {
-        delete t;
-        return tb_fail(TRUSS_EINVAL, "pair[] must be an involution without fixed points");
-      }
-      if (i < j) {
-        pairs.push_back((int16_t)i);
-        pairs.push_back((int16_t)j);
-      }
+  return TRUSS_OK;
+}
+
+// ---- vertical pairs: the (lo, hi) list; false when pair[] is not an involution without fixed points ----
+static bool tb_vertical_pairs(const int32_t *pair, int N, std::vector<int16_t> &pairs) {
+  for (int i = 0; pair && i < N; ++i) {
+    const int j = pair[i];
+    if (j < 0 || j >= N || j == i || pair[j] != i) return false;
+    if (i < j) {
+      pairs.push_back((int16_t)i);
+      pairs.push_back((int16_t)j);
     }
   }
-  t->NP = (int)pairs.size() / 2;
+  return true;
+}
 
-  // ---- node ordering for the banded solver: hint, natural, RCM from every start ----
+// ---- node ordering for the banded solver: hint, natural, RCM from every start; the first candidate with the smallest
+// half-bandwidth `bw` gives dofpos (solver position of node*2+comp, -1 = restrained).  false: the hint is no permutation ----
+static bool tb_node_ordering(const TbInput &in, int &bw, std::vector<int> &dofpos) {
+  const int N = in.N, E = in.E;
   std::vector<std::vector<int>> adj(N);
   for (int e = 0; e < E; ++e) {
-    adj[conn[2 * e]].push_back(conn[2 * e + 1]);
-    adj[conn[2 * e + 1]].push_back(conn[2 * e]);
+    adj[in.conn[2 * e]].push_back(in.conn[2 * e + 1]);
+    adj[in.conn[2 * e + 1]].push_back(in.conn[2 * e]);
   }
   std::vector<std::vector<int>> cands;
-  if (node_order) {
-    std::vector<int> o(node_order, node_order + N);
+  if (in.node_order) {
+    std::vector<int> o(in.node_order, in.node_order + N);
     std::vector<char> seen(N, 0);
-    bool ok = true;
     for (int v : o) {
-      if (v < 0 || v >= N || seen[v]) ok = false;
-      else seen[v] = 1;
-    }
-    if (!ok) {
-      delete t;
-      return tb_fail(TRUSS_EINVAL, "node_order is not a permutation");
+      if (v < 0 || v >= N || seen[v]) return false;
+      seen[v] = 1;
     }
     cands.push_back(o);
   }
-  {
-    std::vector<int> nat(N);
-    for (int i = 0; i < N; ++i) nat[i] = i;
-    cands.push_back(nat);
-  }
+  cands.emplace_back(N);
+  for (int i = 0; i < N; ++i) cands.back()[i] = i;
   for (int s = 0; s < N && N <= 1024; ++s) cands.push_back(tb_rcm(s, adj, N));
   int best = -1, best_bw = 1 << 30;
   for (size_t i = 0; i < cands.size(); ++i) {
-    int bw = tb_bandwidth(cands[i], res, conn, N, E, nullptr);
-    if (bw < best_bw) {
-      best_bw = bw;
+    int b = tb_bandwidth(cands[i], in.res, in.conn, N, E, nullptr);
+    if (b < best_bw) {
+      best_bw = b;
       best = (int)i;
     }
   }
-  std::vector<int> dofpos;
-  t->bw = tb_bandwidth(cands[best], res, conn, N, E, &dofpos);
+  bw = tb_bandwidth(cands[best], in.res, in.conn, N, E, &dofpos);
+  return true;
+}
 
-  // ---- kernel variant: smallest window that holds the band; TRUSS_LANES / TRUSS_RPL override ----
-  // Preference (TRUSS_LANES / TRUSS_WLANES / TRUSS_RPL override): the narrowest window that holds the
-  // band; 16 lanes per env (4 envs per wave) so that a 4096-env batch puts a wave on every SIMD.
+// ---- kernel variant (index into kVariants, -1 = none compiled): the narrowest window that holds the band; 16 lanes per
+// env (4 envs per wave) so that a 4096-env batch puts a wave on every SIMD.  TRUSS_LANES / TRUSS_WLANES / TRUSS_RPL override ----
+static int tb_pick_variant(int bw, int E) {
   int want_G = tb_env_int("TRUSS_LANES", 0), want_WL = tb_env_int("TRUSS_WLANES", 0), want_RPL = tb_env_int("TRUSS_RPL", 0);
   int pick = -1;
-  auto score = [&](const TbVariant &v) {
+  auto score = [](const TbVariant &v) {
     int W = v.WL * v.RPL;
     int pref = (v.G == 16 && v.WL == 8) ? 0 : (v.G == 8 && v.WL == 8) ? 1 : (v.G == 16) ? 2 : 3;
     return W * 10000 + v.RPL * 1000 + pref * 100 + v.EPL;
@@ -437,299 +438,337 @@ extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const
   for (int i = 0; i < kNumVariants; ++i) {
     const TbVariant &v = kVariants[i];
     int W = v.WL * v.RPL;
-    if (W <= t->bw) continue;
+    if (W <= bw) continue;
     if ((E + v.G - 1) / v.G > v.EPL) continue;
     if (want_G && v.G != want_G) continue;
     if (want_WL && v.WL != want_WL) continue;
     if (want_RPL && v.RPL != want_RPL) continue;
     if (pick < 0 || score(v) < score(kVariants[pick])) pick = i;
   }
-  if (pick < 0) {
-    char buf[256];
-    snprintf(buf, sizeof buf,
-             "no compiled kernel for half-bandwidth %d with %d elements (windows: 8, 16; up to 640 elements)", t->bw, E);
-    delete t;
-    return tb_fail(TRUSS_EUNSUPPORTED, buf);
-  }
-  t->variant = pick;
-  t->G = kVariants[pick].G;
-  t->WL = kVariants[pick].WL;
-  t->RPL = kVariants[pick].RPL;
-  t->EPL = kVariants[pick].EPL;
-  t->W = t->WL * t->RPL;
-  const int W = t->W;
-  t->n_pad = ((t->ndof + W - 1) / W) * W;
-  // ---- solver geometry (see TopoDev) ----
-  const int n = t->ndof;
-  const int nteams = (t->G / t->WL >= 2 && t->RPL == 1 && !tb_env_int("TRUSS_ONE_SIDED", 0)) ? 2 : 1;
-  int KA, mid, rowsA, rowsB, zlen, dlen, zslot;
-  if (nteams == 2) {
-    KA = n > W ? (n - W + 1) / 2 : 0;
-    mid = n - 2 * KA;
-    rowsA = KA + 2 * W;
-    rowsB = KA + W;
-    zlen = KA + 2 * W;
-    dlen = KA + 2 * W;
-    zslot = n + 2 * W;
-  } else {
-    KA = t->n_pad;
-    mid = 0;
-    rowsA = t->n_pad + W;
-    rowsB = 0;
-    zlen = t->n_pad + W;
-    dlen = t->n_pad + W;
-    zslot = t->n_pad;
+  return pick;
+}
+
+// ---- solver geometry (see TopoDev): one team, or two that eliminate from both ends (TRUSS_ONE_SIDED: diagnostic) ----
+struct TbGeometry {
+  int nteams, W, n, KA, mid, rowsA, rowsB, zlen, dlen, zslot;
+  explicit TbGeometry(const truss_topo &t) : W(t.W), n(t.ndof) {
+    nteams = (t.G / t.WL >= 2 && t.RPL == 1 && !tb_env_int("TRUSS_ONE_SIDED", 0)) ? 2 : 1;
+    if (nteams == 2) {
+      KA = n > W ? (n - W + 1) / 2 : 0;
+      mid = n - 2 * KA;
+      rowsA = KA + 2 * W;
+      rowsB = KA + W;
+      zlen = dlen = KA + 2 * W;
+      zslot = n + 2 * W;
+    } else {
+      KA = t.n_pad;
+      mid = 0;
+      rowsA = t.n_pad + W;
+      rowsB = 0;
+      zlen = dlen = t.n_pad + W;
+      zslot = t.n_pad;
+    }
   }
   // offset (in doubles) of the lower-band entry (r, c), r >= c, original solver positions.  A band row
   // stores its W entries by COLUMN RESIDUE in the owning team's frame: entry (row, col) at row*W + col%W
   // (distinct for the W consecutive columns of a row), which is the order of the solver's window registers.
-  auto band_off = [&](int r, int c) -> int {
+  int band_off(int r, int c) const {
     if (nteams == 1 || r < n - KA) return r * W + (c % W);              // team A: its part + middle rows
     int rb = n - 1 - r, cb = n - 1 - c;                                    // team B frame: cb >= rb
     return (rowsA + cb) * W + (rb % W);
-  };
+  }
+  // a spare double right behind the band: sink for entries on restrained DOFs
+  int trash_off() const { return (rowsA + rowsB) * W; }
+};
 
-  const int trash_off = (rowsA + rowsB) * W;  // a spare double right behind the band: sink for entries on restrained DOFs
-
-  // solver position -> reference DOF (0-based) and node*2+comp
-  t->perm.assign(t->ndof, -1);
-  std::vector<int16_t> posnode(t->n_pad, -1), dofpos16(2 * N, -1), restslot(2 * N, -1);
-  for (int i = 0; i < 2 * N; ++i) {
+// ---- topology tables ----
+// solver position -> reference DOF (t.perm, 0-based) and node*2+comp; node*2+comp -> solver position / reaction slot
+static void tb_position_tables(truss_topo &t, const std::vector<int> &dofpos, std::vector<int16_t> &posnode,
+                               std::vector<int16_t> &dofpos16, std::vector<int16_t> &restslot) {
+  t.perm.assign(t.ndof, -1);
+  posnode.assign(t.n_pad, -1);
+  dofpos16.assign(2 * t.N, -1);
+  restslot.assign(2 * t.N, -1);
+  for (int i = 0; i < 2 * t.N; ++i) {
     if (dofpos[i] >= 0) {
-      t->perm[dofpos[i]] = t->nsc[i] - 1;
+      t.perm[dofpos[i]] = t.nsc[i] - 1;
       posnode[dofpos[i]] = (int16_t)i;
       dofpos16[i] = (int16_t)dofpos[i];
     } else {
-      restslot[i] = (int16_t)(t->nsc[i] - t->ndof - 1);
+      restslot[i] = (int16_t)(t.nsc[i] - t.ndof - 1);
     }
   }
-  // band offsets of every element's four off-diagonal entries (FEM_2Dtruss.py:320-324 restricted to the
-  // lower band); the node-diagonal blocks go through `diagoff` below
-  std::vector<int16_t> asm_code(4 * (size_t)E, -1);
+}
+
+// band offsets of every element's four off-diagonal entries (FEM_2Dtruss.py:320-324 restricted to the lower band); the
+// node-diagonal blocks go through tb_diag_offsets.  false: an entry lies outside the window or its offset beyond int16
+static bool tb_asm_codes(const TbGeometry &g, const TbInput &in, const std::vector<int> &dofpos, std::vector<int16_t> &asm_code) {
+  asm_code.assign(4 * (size_t)in.E, -1);
   bool band_ok = true;
-  for (int e = 0; e < E; ++e) {
-    int a = conn[2 * e], b = conn[2 * e + 1];
-    int pa[2] = {dofpos[2 * a], dofpos[2 * a + 1]}, pb[2] = {dofpos[2 * b], dofpos[2 * b + 1]};
-    int cnt = 0;
-    auto add = [&](int r, int c) {
-      int code = trash_off;
+  for (int e = 0; e < in.E; ++e) {
+    const int *pa = &dofpos[2 * in.conn[2 * e]], *pb = &dofpos[2 * in.conn[2 * e + 1]];
+    const int rc[4][2] = {{pa[0], pb[0]}, {pa[1], pb[1]}, {pa[0], pb[1]}, {pa[1], pb[0]}};
+    for (int q = 0; q < 4; ++q) {
+      int r = rc[q][0], c = rc[q][1], code = g.trash_off();
       if (r >= 0 && c >= 0) {
         if (r < c) std::swap(r, c);
-        if (r - c >= W) band_ok = false;
-        code = band_off(r, c);
+        if (r - c >= g.W) band_ok = false;
+        code = g.band_off(r, c);
         if (code > 32767) band_ok = false;
       }
-      asm_code[4 * (size_t)e + cnt++] = (int16_t)code;
-    };
-    add(pa[0], pb[0]);
-    add(pa[1], pb[1]);
-    add(pa[0], pb[1]);
-    add(pa[1], pb[0]);
-    for (int i = 0; i < 2; ++i)   // the node's own x/y pair must fit the band too
-      for (int j = 0; j < 2; ++j) {
-        const int *pp = i ? pb : pa;
-        if (pp[0] >= 0 && pp[1] >= 0 && std::abs(pp[0] - pp[1]) >= W) band_ok = false;
-        (void)j;
-      }
+      asm_code[4 * (size_t)e + q] = (int16_t)code;
+    }
   }
-  if (!band_ok) {
-    delete t;
-    return tb_fail(TRUSS_EUNSUPPORTED, "internal: band wider than window / offsets beyond int16");
-  }
-  // band offsets of the node-diagonal 2x2 block entries (x,x), (y,y), (x,y)
-  std::vector<int16_t> diagoff(3 * (size_t)N, (int16_t)trash_off);
+  for (int nd = 0; nd < in.N; ++nd)   // a node's own x/y pair must fit the band too
+    if (dofpos[2 * nd] >= 0 && dofpos[2 * nd + 1] >= 0 && std::abs(dofpos[2 * nd] - dofpos[2 * nd + 1]) >= g.W) band_ok = false;
+  return band_ok;
+}
+
+// band offsets of the node-diagonal 2x2 block entries (x,x), (y,y), (x,y)
+static std::vector<int16_t> tb_diag_offsets(const TbGeometry &g, int N, const std::vector<int> &dofpos) {
+  std::vector<int16_t> diagoff(3 * (size_t)N, (int16_t)g.trash_off());
   for (int nd = 0; nd < N; ++nd) {
     int px = dofpos[2 * nd], py = dofpos[2 * nd + 1];
-    if (px >= 0) diagoff[3 * nd + 0] = (int16_t)band_off(px, px);
-    if (py >= 0) diagoff[3 * nd + 1] = (int16_t)band_off(py, py);
-    if (px >= 0 && py >= 0) diagoff[3 * nd + 2] = (int16_t)band_off(std::max(px, py), std::min(px, py));
+    if (px >= 0) diagoff[3 * nd + 0] = (int16_t)g.band_off(px, px);
+    if (py >= 0) diagoff[3 * nd + 1] = (int16_t)g.band_off(py, py);
+    if (px >= 0 && py >= 0) diagoff[3 * nd + 2] = (int16_t)g.band_off(std::max(px, py), std::min(px, py));
   }
-  std::vector<int16_t> conn16(2 * (size_t)E);
-  for (int i = 0; i < 2 * E; ++i) conn16[i] = (int16_t)conn[i];
+  return diagoff;
+}
+
+static std::vector<uint8_t> tb_node_flags(const TbInput &in) {
+  const int N = in.N;
   std::vector<uint8_t> nflags(N, 0);
   for (int n = 0; n < N; ++n) {
     uint8_t f = 0;
-    if (top[n]) f |= TF_TOP;
-    if (res[2 * n]) f |= TF_RESX;
-    if (res[2 * n + 1]) f |= TF_RESY;
-    bool lb, lr;
-    if (load_mask) {
-      lb = load_mask[n] != 0;
-      lr = load_mask[N + n] != 0;
-    } else {  // truss2D_GEN.py:421-430
-      lb = !top[n] && res[2 * n + 1] == 0;
-      lr = top[n] != 0;
-    }
-    if (lb) f |= TF_LOAD_BRIDGE;
-    if (lr) f |= TF_LOAD_ROOF;
+    if (in.top[n]) f |= TF_TOP;
+    if (in.res[2 * n]) f |= TF_RESX;
+    if (in.res[2 * n + 1]) f |= TF_RESY;
+    // loaded as a bridge / as a roof: the caller's mask, else truss2D_GEN.py:421-430
+    if (in.load_mask ? in.load_mask[n] != 0 : !in.top[n] && in.res[2 * n + 1] == 0) f |= TF_LOAD_BRIDGE;
+    if (in.load_mask ? in.load_mask[N + n] != 0 : in.top[n] != 0) f |= TF_LOAD_ROOF;
     nflags[n] = f;
   }
-  std::vector<int16_t> symn(2 * (size_t)n_sym_nodes), syme(2 * (size_t)n_sym_elems);
-  for (int i = 0; i < 2 * n_sym_nodes; ++i) symn[i] = (int16_t)sym_nodes[i];
-  for (int i = 0; i < 2 * n_sym_elems; ++i) syme[i] = (int16_t)sym_elems[i];
-  std::vector<double> area(n_sections);
-  for (int i = 0; i < n_sections; ++i) area[i] = sections[2 * i];
+  return nflags;
+}
 
-  std::vector<double> isr(n_sections);
-  for (int i = 0; i < n_sections; ++i) isr[i] = 1.0 / (area[i] * long_stress);
-  std::vector<char> blob;
-  size_t o_conn = tb_push(blob, conn16), o_pairs = tb_push(blob, pairs), o_nf = tb_push(blob, nflags);
-  size_t o_dp = tb_push(blob, dofpos16), o_rs = tb_push(blob, restslot), o_asm = tb_push(blob, asm_code);
-  size_t o_pn = tb_push(blob, posnode), o_sn = tb_push(blob, symn), o_se = tb_push(blob, syme);
-  // elements incident to each node (ascending element index), padded to 8 with E = "zero slot"
-  std::vector<int16_t> adj8((size_t)N * 8, (int16_t)E);
-  for (int n = 0; n < N; ++n) {
+// elements incident to each node (ascending element index), padded to 8 with E = "zero slot"; false: a node joins more
+static bool tb_adjacency8(const TbInput &in, std::vector<int16_t> &adj8) {
+  adj8.assign((size_t)in.N * 8, (int16_t)in.E);
+  for (int n = 0; n < in.N; ++n) {
     int c = 0;
-    for (int e = 0; e < E; ++e)
-      if (conn[2 * e] == n || conn[2 * e + 1] == n) {
-        if (c >= 8) {
-          delete t;
-          return tb_fail(TRUSS_EUNSUPPORTED, "a node joins more than 8 elements");
-        }
+    for (int e = 0; e < in.E; ++e)
+      if (in.conn[2 * e] == n || in.conn[2 * e + 1] == n) {
+        if (c >= 8) return false;
         adj8[(size_t)n * 8 + c++] = (int16_t)e;
       }
   }
-  size_t o_ar = tb_push(blob, area), o_isr = tb_push(blob, isr);
-  std::vector<float> areaf(n_sections), vsf(n_sections);
-  for (int i = 0; i < n_sections; ++i) {
-    areaf[i] = (float)area[i];
-    vsf[i] = (float)(area[i] / area[n_sections - 1]);   // truss2D_ENV.py:86-87 (area / truss[-1] area)
-  }
-  size_t o_arf = tb_push(blob, areaf), o_vsf = tb_push(blob, vsf);
-  // load code of every z/P slot in team frames (see TopoDev::f_zcode)
-  std::vector<uint8_t> zcode((size_t)zlen * nteams, 0);
-  for (int tm = 0; tm < nteams; ++tm)
-    for (int pz = 0; pz < zlen; ++pz) {
+  return true;
+}
+
+// load code of every z/P slot in team frames (see TopoDev::f_zcode)
+static std::vector<uint8_t> tb_load_codes(const TbGeometry &g, const std::vector<int16_t> &posnode, const std::vector<uint8_t> &nflags) {
+  std::vector<uint8_t> zcode((size_t)g.zlen * g.nteams, 0);
+  for (int tm = 0; tm < g.nteams; ++tm)
+    for (int pz = 0; pz < g.zlen; ++pz) {
       int orig = -1;
-      if (nteams == 1) orig = pz < n ? pz : -1;
-      else if (tm == 0) orig = pz < n - KA ? pz : -1;
-      else orig = pz < KA ? n - 1 - pz : -1;
+      if (g.nteams == 1) orig = pz < g.n ? pz : -1;
+      else if (tm == 0) orig = pz < g.n - g.KA ? pz : -1;
+      else orig = pz < g.KA ? g.n - 1 - pz : -1;
       if (orig < 0) continue;
       int nd = posnode[orig];
       if (nd < 0) continue;
       uint8_t fl = nflags[nd >> 1];
-      zcode[(size_t)tm * zlen + pz] = (uint8_t)((nd & 1) | ((fl & TF_LOAD_BRIDGE) ? 2 : 0) | ((fl & TF_LOAD_ROOF) ? 4 : 0));
+      zcode[(size_t)tm * g.zlen + pz] = (uint8_t)((nd & 1) | ((fl & TF_LOAD_BRIDGE) ? 2 : 0) | ((fl & TF_LOAD_ROOF) ? 4 : 0));
     }
-  // slots of every element's four end displacements in the solution vector (restrained -> the zero slot)
-  std::vector<int16_t> exs(4 * (size_t)E);
-  for (int e = 0; e < E; ++e)
+  return zcode;
+}
+
+// slots of every element's four end displacements in the solution vector (restrained -> the zero slot)
+static std::vector<int16_t> tb_solution_slots(const TbGeometry &g, const TbInput &in, const std::vector<int> &dofpos) {
+  std::vector<int16_t> exs(4 * (size_t)in.E);
+  for (int e = 0; e < in.E; ++e)
     for (int q = 0; q < 4; ++q) {
-      const int dp = dofpos[2 * conn[2 * e + (q >> 1)] + (q & 1)];
-      exs[4 * (size_t)e + q] = (int16_t)(dp < 0 ? zslot : dp);
+      const int dp = dofpos[2 * in.conn[2 * e + (q >> 1)] + (q & 1)];
+      exs[4 * (size_t)e + q] = (int16_t)(dp < 0 ? g.zslot : dp);
     }
-  size_t o_ad = tb_push(blob, adj8), o_do = tb_push(blob, diagoff), o_zc = tb_push(blob, zcode), o_exs = tb_push(blob, exs);
+  return exs;
+}
+
+static std::vector<int16_t> tb_int16(const int32_t *p, size_t n) { return std::vector<int16_t>(p, p + n); }
+
+// every table of the step kernel, packed into `blob`; the ORDER of the pushes is the blob layout.  Fills the counts, the
+// solver geometry and the f_* offsets of t.dev.  Refuses (band guard, then node degree) before anything is pushed.
+static int tb_build_tables(truss_topo &t, const TbGeometry &g, const TbInput &in, const std::vector<int> &dofpos,
+                           const std::vector<int16_t> &pairs, std::vector<char> &blob) {
+  const int S = in.n_sections;
+  std::vector<int16_t> posnode, dofpos16, restslot, asm_code, adj8;
+  tb_position_tables(t, dofpos, posnode, dofpos16, restslot);
+  if (!tb_asm_codes(g, in, dofpos, asm_code))
+    return tb_fail(TRUSS_EUNSUPPORTED, "internal: band wider than window / offsets beyond int16");
+  if (!tb_adjacency8(in, adj8)) return tb_fail(TRUSS_EUNSUPPORTED, "a node joins more than 8 elements");
+  const std::vector<uint8_t> nflags = tb_node_flags(in);
+  std::vector<double> area(S), isr(S);
+  std::vector<float> areaf(S), vsf(S);
+  for (int i = 0; i < S; ++i) {
+    area[i] = in.sections[2 * i];
+    isr[i] = 1.0 / (area[i] * in.long_stress);
+    areaf[i] = (float)area[i];
+    vsf[i] = (float)(area[i] / in.sections[2 * (S - 1)]);   // truss2D_ENV.py:86-87 (area / truss[-1] area)
+  }
+  TopoDev &D = t.dev;
+  D.N = t.N;
+  D.E = t.E;
+  D.NP = t.NP;
+  D.ndof = t.ndof;
+  D.n_pad = t.n_pad;
+  D.n_rest = t.n_rest;
+  D.n_sym_nodes = in.n_sym_nodes;
+  D.n_sym_elems = in.n_sym_elems;
+  D.n_sections = S;
+  D.has_pairs = t.NP > 0 && 2 * t.NP == t.N;
+  D.nteams = g.nteams;
+  D.KA = g.KA;
+  D.mid = g.mid;
+  D.rowsA = g.rowsA;
+  D.rowsB = g.rowsB;
+  D.zlen = g.zlen;
+  D.dlen = g.dlen;
+  D.zslot = g.zslot;
+  D.e_mod = in.e_mod;
+  D.long_stress = in.long_stress;
+  D.f_conn = tb_push(blob, tb_int16(in.conn, 2 * (size_t)t.E));
+  D.f_pairs = tb_push(blob, pairs);
+  D.f_nflags = tb_push(blob, nflags);
+  D.f_dofpos = tb_push(blob, dofpos16);
+  D.f_restslot = tb_push(blob, restslot);
+  D.f_asm = tb_push(blob, asm_code);
+  D.f_posnode = tb_push(blob, posnode);
+  D.f_symn = tb_push(blob, tb_int16(in.sym_nodes, 2 * (size_t)in.n_sym_nodes));
+  D.f_syme = tb_push(blob, tb_int16(in.sym_elems, 2 * (size_t)in.n_sym_elems));
+  D.f_area = tb_push(blob, area);
+  D.f_isr = tb_push(blob, isr);
+  D.f_areaf = tb_push(blob, areaf);
+  D.f_vsf = tb_push(blob, vsf);
+  D.f_adj8 = tb_push(blob, adj8);
+  D.f_diagoff = tb_push(blob, tb_diag_offsets(g, t.N, dofpos));
+  D.f_zcode = tb_push(blob, tb_load_codes(g, posnode, nflags));
+  D.f_exs = tb_push(blob, tb_solution_slots(g, in, dofpos));
   blob.resize((blob.size() + 15) & ~size_t(15));
-  TopoDev &D = t->dev;
-  D.N = N;
-  D.E = E;
-  D.NP = t->NP;
-  D.ndof = t->ndof;
-  D.n_pad = t->n_pad;
-  D.n_rest = t->n_rest;
-  D.n_sym_nodes = n_sym_nodes;
-  D.n_sym_elems = n_sym_elems;
-  D.n_sections = n_sections;
-  D.has_pairs = t->NP > 0 && 2 * t->NP == N;
   D.blob_bytes = (int32_t)blob.size();
-  D.f_conn = (int32_t)o_conn;
-  D.f_pairs = (int32_t)o_pairs;
-  D.f_nflags = (int32_t)o_nf;
-  D.f_dofpos = (int32_t)o_dp;
-  D.f_restslot = (int32_t)o_rs;
-  D.f_asm = (int32_t)o_asm;
-  D.f_posnode = (int32_t)o_pn;
-  D.f_symn = (int32_t)o_sn;
-  D.f_syme = (int32_t)o_se;
-  D.f_area = (int32_t)o_ar;
-  D.f_isr = (int32_t)o_isr;
-  D.f_areaf = (int32_t)o_arf;
-  D.f_vsf = (int32_t)o_vsf;
-  D.f_adj8 = (int32_t)o_ad;
-  D.f_diagoff = (int32_t)o_do;
-  D.f_zcode = (int32_t)o_zc;
-  D.f_exs = (int32_t)o_exs;
-  D.nteams = nteams;
-  D.KA = KA;
-  D.mid = mid;
-  D.rowsA = rowsA;
-  D.rowsB = rowsB;
-  D.zlen = zlen;
-  D.dlen = dlen;
-  D.zslot = zslot;
-  D.e_mod = e_mod;
-  D.long_stress = long_stress;
-  // LDS layout: [copy of the blob][env 0][env 1]...; every array 16-byte aligned
+  return TRUSS_OK;
+}
+
+// ---- LDS layout: [copy of the tables][env 0][env 1]...; every array 16-byte aligned.  Fills o_*, so_*, env_stride and o_env0
+// of t.dev and t.lds_bytes; early / late: the dead bytes of an env for the bank of the fused observation writer (tb_build_emit) ----
+struct TbCarve {   // byte offsets of arrays laid out one behind the other
   size_t off = 0;
-  std::vector<TbFrag> fr_early, fr_late;   // dead bytes for the bank of the fused observation writer (tb_build_emit)
-  auto carve = [&](size_t bytes) {
+  int32_t operator()(size_t bytes) {
     size_t o = off;
     off = (off + bytes + 15) & ~size_t(15);
     return (int32_t)o;
-  };
+  }
+  void at_least(size_t o0, size_t need) {   // the region that began at o0 holds `need` bytes or more
+    if (off - o0 < need) off = (o0 + need + 15) & ~size_t(15);
+  }
+};
+static void tb_lds_layout(truss_topo &t, const TbGeometry &g, size_t table_bytes, std::vector<TbFrag> &early, std::vector<TbFrag> &late) {
+  TopoDev &D = t.dev;
+  const int N = t.N, E = t.E, W = g.W;
+  TbCarve carve;
   // band region; after the back substitution it is reused as the output staging area
   {
-    size_t band = sizeof(double) * ((size_t)(rowsA + rowsB) * W + 2);  // + trash slot
-    size_t so = 0;
-    auto sub = [&](size_t bytes) {
-      size_t o = so;
-      so = (so + bytes + 15) & ~size_t(15);
-      return (int32_t)o;
-    };
+    const size_t band = sizeof(double) * ((size_t)(g.rowsA + g.rowsB) * W + 2);  // + trash slot
+    TbCarve sub;
     D.so_q0 = sub(sizeof(float) * E);
     D.so_sr = sub(sizeof(float) * E);
     D.so_disp = sub(sizeof(float) * 2 * N);
     D.so_mu = sub(sizeof(float) * N);
     D.so_md = sub(sizeof(float) * N);
     D.so_comp = sub((size_t)E);
-    D.o_red = -1;  // set below: objective partials live behind the staging rows (the band is dead by then)
-    size_t red_off = so;
-    so += sizeof(double) * TRUSS_NRED * (size_t)t->G;
+    const size_t red_off = sub.off;   // objective partials live behind the staging rows (the band is dead by then)
+    const size_t so = red_off + sizeof(double) * TRUSS_NRED * (size_t)t.G;
     D.o_kb = carve(std::max(band, so));
     D.o_red = D.o_kb + (int32_t)red_off;
-    fr_early.push_back({(size_t)D.o_kb + so, (size_t)D.o_kb + std::max(band, so)});
+    early.push_back({(size_t)D.o_kb + so, (size_t)D.o_kb + std::max(band, so)});
   }
   // solver scratch; before the solver the same bytes hold the per-element (k cc, k cs, k ss), after
   // the back substitution `red` (objective partials) reuses the z vectors
   {
-    size_t o0 = off;
-    D.o_zs = carve(sizeof(double) * (size_t)zlen * nteams);  // z vector per team (zlen is even)
-    D.o_xsol = carve(sizeof(double) * (zslot + 4));  // + zero slot, dummy slot, 16-byte fill
-    D.o_rbuf = carve(sizeof(double) * std::max(t->n_rest, 1));
-    D.o_zring = carve(sizeof(double) * W * nteams);   // per-lane trash slots
+    const size_t o0 = carve.off;
+    D.o_zs = carve(sizeof(double) * (size_t)g.zlen * g.nteams);  // z vector per team (zlen is even)
+    D.o_xsol = carve(sizeof(double) * (g.zslot + 4));  // + zero slot, dummy slot, 16-byte fill
+    D.o_rbuf = carve(sizeof(double) * std::max(t.n_rest, 1));
+    D.o_zring = carve(sizeof(double) * W * g.nteams);   // per-lane trash slots
     D.o_ev = (int32_t)o0;
-    size_t need = sizeof(double) * 3 * ((size_t)E + 1);
-    if (off - o0 < need) off = (o0 + need + 15) & ~size_t(15);
-    fr_late.push_back({o0, (size_t)D.o_rbuf});                     // z vectors, solution vector
-    fr_late.push_back({(size_t)D.o_zring, off});                    // behind the reactions
+    carve.at_least(o0, sizeof(double) * 3 * ((size_t)E + 1));
+    late.push_back({o0, (size_t)D.o_rbuf});                     // z vectors, solution vector
+    late.push_back({(size_t)D.o_zring, carve.off});              // behind the reactions
   }
   D.o_par = carve(sizeof(double) * 8);
   D.o_y = carve(sizeof(float) * N);
   D.o_x = carve(sizeof(float) * N);
   D.o_tg = carve(sizeof(float) * N);
   {
-    size_t o0 = off;
+    const size_t o0 = carve.off;
     D.o_geo = carve(sizeof(float) * 2 * N);
     D.o_tac = carve(sizeof(float) * 3 * N);
     D.o_mrg = (int32_t)o0;  // merge scratch of the two-sided solver: the actions are dead by then
-    size_t need = nteams == 2 ? sizeof(double) * (size_t)(W * W + W) : 0;
-    if (off - o0 < need) off = (o0 + need + 15) & ~size_t(15);
-    fr_early.push_back({o0, off});
+    carve.at_least(o0, g.nteams == 2 ? sizeof(double) * (size_t)(W * W + W) : 0);
+    early.push_back({o0, carve.off});
   }
   D.o_sec = carve(sizeof(int32_t) * E);
   // stagger env regions across LDS banks: stride = 64 B (mod 256 B)
-  size_t stride = (off + 255) & ~size_t(255);
-  stride += 64;
+  const size_t stride = ((carve.off + 255) & ~size_t(255)) + 64;
   D.env_stride = (int32_t)stride;
-  D.o_env0 = (int32_t)((blob.size() + 255) & ~size_t(255));
-  t->lds_bytes = D.o_env0 + stride * (64 / t->G);
-  tb_build_emit(t, conn, res, top, fr_early, fr_late, blob);   // may append the LDS-resident nN_x_e table to the blob
-  t->blob = tb_dev_alloc(blob.size());
-  if (!t->blob || !tb_dev_upload(t->blob, blob.data(), blob.size())) {
-    if (t->blob) tb_dev_free(t->blob);
-    if (t->etab) tb_dev_free(t->etab);
-    delete t;
-    return tb_fail(TRUSS_ENOMEM, "device allocation/upload of topology tables failed");
+  D.o_env0 = (int32_t)((table_bytes + 255) & ~size_t(255));
+  t.lds_bytes = D.o_env0 + stride * (64 / t.G);
+}
+
+extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const int32_t *conn, const uint8_t *res,
+                                 const uint8_t *top, const int32_t *pair, const uint8_t *load_mask,
+                                 int32_t n_sym_nodes, const int32_t *sym_nodes, int32_t n_sym_elems,
+                                 const int32_t *sym_elems, int32_t n_sections, const double *sections, double e_mod,
+                                 double long_stress, const int32_t *node_order) {
+  const TbInput in{N, E, conn, res, top, pair, load_mask, n_sym_nodes, sym_nodes, n_sym_elems, sym_elems, n_sections, sections,
+                   e_mod, long_stress, node_order};
+  if (int rc = tb_check_args(out, in)) return rc;
+  std::unique_ptr<truss_topo> t(new truss_topo());   // every refusal below just returns: ~truss_topo frees what exists by then
+  t->N = N;
+  t->E = E;
+  t->n_sections = n_sections;
+  tb_dof_numbering(*t, conn, res);
+  if (t->ndof < 1) return tb_fail(TRUSS_EINVAL, "no free DOF");
+  std::vector<int16_t> pairs;
+  if (!tb_vertical_pairs(pair, N, pairs)) return tb_fail(TRUSS_EINVAL, "pair[] must be an involution without fixed points");
+  t->NP = (int)pairs.size() / 2;
+  std::vector<int> dofpos;
+  if (!tb_node_ordering(in, t->bw, dofpos)) return tb_fail(TRUSS_EINVAL, "node_order is not a permutation");
+  t->variant = tb_pick_variant(t->bw, E);
+  if (t->variant < 0) {
+    char buf[256];
+    snprintf(buf, sizeof buf,
+             "no compiled kernel for half-bandwidth %d with %d elements (windows: 8, 16; up to 640 elements)", t->bw, E);
+    return tb_fail(TRUSS_EUNSUPPORTED, buf);
   }
+  const TbVariant &v = kVariants[t->variant];
+  t->G = v.G;
+  t->WL = v.WL;
+  t->RPL = v.RPL;
+  t->EPL = v.EPL;
+  t->W = v.WL * v.RPL;
+  t->n_pad = ((t->ndof + t->W - 1) / t->W) * t->W;
+  const TbGeometry g(*t);
+  std::vector<char> blob;
+  if (int rc = tb_build_tables(*t, g, in, dofpos, pairs, blob)) return rc;
+  std::vector<TbFrag> fr_early, fr_late;
+  tb_lds_layout(*t, g, blob.size(), fr_early, fr_late);
+  tb_build_emit(t.get(), conn, res, top, fr_early, fr_late, blob);   // may append the LDS-resident nN_x_e table to the blob
+  t->blob = tb_dev_alloc(blob.size());
+  if (!t->blob || !tb_dev_upload(t->blob, blob.data(), blob.size()))
+    return tb_fail(TRUSS_ENOMEM, "device allocation/upload of topology tables failed");
+  TopoDev &D = t->dev;
+  const size_t stride = (size_t)D.env_stride;
   D.blob = (const char *)t->blob;
   t->dev_emit = D;
   t->dev_emit.blob_bytes = (int32_t)blob.size();
@@ -741,25 +780,17 @@ extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const
     fprintf(stderr,
             "[truss_mi355] N=%d E=%d ndof=%d bw=%d | G=%d WL=%d RPL=%d EPL=%d teams=%d KA=%d mid=%d | tables %d B, "
             "env %zu B, LDS/workgroup %zu B (%zu workgroups/CU), fused observation writer %s\n",
-            N, E, t->ndof, t->bw, t->G, t->WL, t->RPL, t->EPL, nteams, KA, mid, D.blob_bytes, stride, t->lds_bytes,
+            N, E, t->ndof, t->bw, t->G, t->WL, t->RPL, t->EPL, g.nteams, g.KA, g.mid, D.blob_bytes, stride, t->lds_bytes,
             (size_t)(160 * 1024) / t->lds_bytes, D.emit_ok ? "yes" : "no");
   if (tb_env_int("TRUSS_VERBOSE", 0) && D.emit_ok)
     fprintf(stderr, "[truss_mi355]   fused launch: tables %d B, LDS/workgroup %zu B (%zu workgroups/CU)\n", t->dev_emit.blob_bytes,
             t->lds_bytes_emit, (size_t)(160 * 1024) / t->lds_bytes_emit);
-  if (t->lds_bytes > 160 * 1024) {
-    tb_dev_free(t->blob);
-    if (t->etab) tb_dev_free(t->etab);
-    delete t;
-    return tb_fail(TRUSS_EUNSUPPORTED, "topology needs more than 160 KiB of LDS per workgroup");
-  }
-  *out = t;
+  if (t->lds_bytes > 160 * 1024) return tb_fail(TRUSS_EUNSUPPORTED, "topology needs more than 160 KiB of LDS per workgroup");
+  *out = t.release();
   return TRUSS_OK;
 }
 
 extern "C" int truss_topo_destroy(truss_topo_t *t) {
-  if (!t) return TRUSS_OK;
-  if (t->blob) tb_dev_free(t->blob);
-  if (t->etab) tb_dev_free(t->etab);
   delete t;
   return TRUSS_OK;
 }
@@ -837,6 +868,14 @@ static int tb_make_step_args(const truss_topo_t *t, const truss_step_args_t *a, 
   return TRUSS_OK;
 }
 
+// Arguments of an observation launch: `O` lists B, flags and the tensors in the order of ObsArgsDev's fields; the row tiling of the
+// N x N matrices (tile_rows / n_split, the two fields behind them) is decided here
+static ObsArgsDev tb_obs_args(int N, ObsArgsDev O) {
+  O.tile_rows = tb_obs_tile_rows(N);
+  O.n_split = tb_obs_splits(N) ? (N + O.tile_rows - 1) / O.tile_rows : 1;
+  return O;
+}
+
 // One step; with TRUSS_F_EMIT_OBS the observation tensors come from the same launch where the topology allows
 // it (dev.emit_ok) and from the observation kernel, launched right behind the step on the same stream, elsewhere.
 static int tb_step_dispatch(const truss_topo *t, const StepArgsDev &D, void *stream) {
@@ -844,29 +883,8 @@ static int tb_step_dispatch(const truss_topo *t, const StepArgsDev &D, void *str
   if (t->dev.emit_ok) return tb_launch_step(t, D, true, stream);
   int rc = tb_launch_step(t, D, false, stream);
   if (rc != TRUSS_OK) return rc;
-  ObsArgsDev O;
-  O.B = D.B;
-  O.flags = 0;
-  O.x = D.x;
-  O.y = D.y_out;
-  O.sec = D.sec_out;
-  O.mu = D.mu_out;
-  O.md = D.md_out;
-  O.target = D.target;
-  O.disp = D.disp;
-  O.q0 = D.q0;
-  O.sr = D.sr;
-  O.comp = D.comp;
-  O.env_params = D.env_params;
-  O.x_n = D.x_n;
-  O.A_s = D.A_s;
-  O.A_ts = D.A_ts;
-  O.A_cs = D.A_cs;
-  O.nxn = D.nxn;
-  O.nxe = D.nxe;
-  O.tile_rows = tb_obs_tile_rows(t->N);
-  O.n_split = tb_obs_splits(t->N) ? (t->N + O.tile_rows - 1) / O.tile_rows : 1;
-  return tb_launch_obs(t, O, stream);
+  return tb_launch_obs(t, tb_obs_args(t->N, {D.B, 0, D.x, D.y_out, D.sec_out, D.mu_out, D.md_out, D.target, D.disp, D.q0, D.sr, D.comp,
+                                             D.env_params, D.x_n, D.A_s, D.A_ts, D.A_cs, D.nxn, D.nxe}), stream);
 }
 
 // the persistent rollout kernel keeps rows in LDS with the staging fast path's 16-byte accesses: same conditions
@@ -929,27 +947,7 @@ extern "C" int truss_obs(const truss_topo_t *t, const truss_obs_args_t *a, void 
     return tb_fail(TRUSS_EINVAL, "a required device pointer is NULL");
   if (tb_obs_lds_bytes(t->N) > 160 * 1024) return tb_fail(TRUSS_EUNSUPPORTED, "N too large for the observation kernel");
   // (with row tiles that is N > ~3000)
-  ObsArgsDev D;
-  D.B = a->n_envs;
-  D.flags = a->flags;
-  D.x = a->x;
-  D.y = a->y;
-  D.sec = a->sec;
-  D.mu = a->max_up;
-  D.md = a->max_down;
-  D.target = a->target;
-  D.disp = a->disp;
-  D.q0 = a->q0;
-  D.sr = a->sr;
-  D.comp = a->comp;
-  D.env_params = a->env_params;
-  D.x_n = a->x_n;
-  D.A_s = a->A_s;
-  D.A_ts = a->A_n_ts;
-  D.A_cs = a->A_n_cs;
-  D.nxn = a->nN_x_n;
-  D.nxe = a->nN_x_e;
-  D.tile_rows = tb_obs_tile_rows(t->N);
-  D.n_split = tb_obs_splits(t->N) ? (t->N + D.tile_rows - 1) / D.tile_rows : 1;
-  return tb_launch_obs(t, D, stream);
+  return tb_launch_obs(t, tb_obs_args(t->N, {a->n_envs, a->flags, a->x, a->y, a->sec, a->max_up, a->max_down, a->target, a->disp, a->q0,
+                                             a->sr, a->comp, a->env_params, a->x_n, a->A_s, a->A_n_ts, a->A_n_cs, a->nN_x_n, a->nN_x_e}),
+                       stream);
 }
