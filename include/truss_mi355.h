@@ -310,6 +310,64 @@ typedef struct truss_reward_args {
 } truss_reward_args_t;
 int truss_reward(const truss_reward_args_t *args, void *stream);
 
+/* ---- archive update of a game step, one launch for B envs ---------------------------------------------
+ * replaces: the archive block of master_DDPG_truss2D_MO.run() (:372-436: append the feasible candidates to Pf, simple_cull,
+ * clip the objectives) as truss_mi355/marl.py assembles it around one truss_front launch -- candidate buffers, scatters, two
+ * concatenations of the whole archive, gathers of the surviving designs and the accepted flags.
+ *
+ * Per env b the cull sees P + C rows [obj1, obj2, con1, con2]:
+ *   row i < P      archive row pts_in[b][i]; rows i >= clamp(n_in[b], 0, P) are dead: the cull sees their con1 as 2.0
+ *   row P + c      candidate slot c < C: row r = slot_row[b][c] of the caller's candidate arrays (cand_points / cand_y /
+ *                  cand_sec), r outside [0, n_cand_rows) (-1 by convention) = empty slot; slot_row == NULL: r = b C + c (dense
+ *                  step-wide buffers).  A candidate is ok iff con1 <= 1 && con2 <= 1 (a NaN is not ok).  An empty slot is the
+ *                  infeasible row [0, 0, 2, 0]; a candidate that is not ok keeps its values with con1 = 2.0
+ * The cull, the order (obj1, obj2, input order) and, with max_front >= 2, the truncation by crowding distance are those of
+ * truss_front (above; max_front == 0: no truncation) with the reference point (1, 1): the same selection, bit for bit.
+ * Outputs, rows in front order, every row j >= n_out[b] written as zeros:
+ *   pts_out    the selected row, obj1 / obj2 clamped to <= 1.0 (:434-436)
+ *   y_out / sec_out  the selected design: archive row i of y_in / sec_in, or row r of cand_y / cand_sec (n_y / n_sec words each)
+ *   n_out      size of the front (at most max_front when truncating)
+ *   accepted   [B][C] 1 iff slot c's row is in the new archive (NULL: skipped)
+ *   front_idx  [B][max_out] input row (i, or P + c) of the k-th front point, -1 beyond n_out; hv_front [B], metrics [B][5] as
+ *              truss_front's (each NULL: skipped)
+ * One workgroup per env: one wave for P + C <= 64, 256 threads up to P + C <= 256.  No atomics, every output element has one
+ * owner.  Device pointers; the library neither allocates nor synchronises (capturable in a hipGraph).
+ * TRUSS_EINVAL, with nothing launched or written: bad struct_size, n_envs < 0, P < 1, C < 0, P + C > 256, max_front == 1 or < 0,
+ * max_out < max_front (truncating) or < P + C (not), n_y < 1, n_sec < 1, n_cand_rows < 0 (< B C with slot_row == NULL), a NULL
+ * required pointer (the candidate arrays are required when C > 0), an output range that overlaps an input range or another output
+ * -- the archive cannot be updated in place: the caller keeps two sets of buffers.  n_envs == 0: TRUSS_OK, no launch.
+ * Optional symbol: a library of this ABI version may lack it. */
+#define TRUSS_ARCHIVE_MAXROWS 256
+typedef struct truss_archive_args {
+  size_t struct_size;
+  int32_t n_envs;            /* B */
+  int32_t max_points;        /* P: rows of the archive per env */
+  int32_t n_slots;           /* C: candidate slots per env; P + C <= TRUSS_ARCHIVE_MAXROWS */
+  int32_t max_front;         /* 0: no truncation; else as TRUSS_FRONT_TRUNCATE with this MAX_FRONT (>= 2) */
+  int32_t max_out;           /* row stride of the outputs: >= max_front when truncating, >= P + C otherwise */
+  int32_t n_y, n_sec;        /* words per design row of y / sec */
+  int32_t n_cand_rows;       /* R: rows of the candidate arrays */
+  uint32_t flags;            /* 0 */
+  uint32_t reserved;
+  const double *pts_in;      /* [B][P][4] */
+  const int32_t *n_in;       /* [B] */
+  const float *y_in;         /* [B][P][n_y] */
+  const int32_t *sec_in;     /* [B][P][n_sec] */
+  const int32_t *slot_row;   /* [B][C] or NULL */
+  const double *cand_points; /* [R][4] */
+  const float *cand_y;       /* [R][n_y] */
+  const int32_t *cand_sec;   /* [R][n_sec] */
+  double *pts_out;           /* [B][max_out][4] */
+  float *y_out;              /* [B][max_out][n_y] */
+  int32_t *sec_out;          /* [B][max_out][n_sec] */
+  int32_t *n_out;            /* [B] */
+  uint8_t *accepted;         /* [B][C] or NULL */
+  int32_t *front_idx;        /* [B][max_out] or NULL */
+  double *hv_front;          /* [B] or NULL */
+  double *metrics;           /* [B][5] or NULL */
+} truss_archive_args_t;
+int truss_archive_merge(const truss_archive_args_t *args, void *stream);
+
 /* ---- GCN neighbourhood aggregation for the actors' inference in batched rollouts -----------------
  * replaces (inference only): the `A @ (X W) + b` + activation half of spektral GCNConv as used by
  * truss2D_RL.multimodes_actor (truss2D_RL.py:49-120): out[b][i][c] = act(sum_j A[b][i][j] H[b][j][c] + bias[c])

@@ -37,7 +37,8 @@
   X(gcn_level_backward, truss_gcn_level_backward, false)         \
   X(replay_scatter, truss_replay_scatter, false)                 \
   X(replay_gather, truss_replay_gather, false)                   \
-  X(reward, truss_reward, false)
+  X(reward, truss_reward, false)                                 \
+  X(archive_merge, truss_archive_merge, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -486,6 +487,66 @@ void reward(int64_t lib, int64_t stream, int64_t max_front, const at::Tensor &fr
   check_rc(b, b.reward(&a, (void *)stream), "truss_reward");
 }
 
+// the archive update of a game step for B envs in one launch: cull of the archive rows + the candidate slots, truncation, gather of
+// the surviving designs, accepted flags (master_DDPG_truss2D_MO.py:372-436) == truss_archive_merge
+void archive_merge(int64_t lib, int64_t stream, int64_t max_front, int64_t n_slots, const at::Tensor &pts_in, const at::Tensor &n_in,
+                   const at::Tensor &y_in, const at::Tensor &sec_in, const OT &slot_row, const at::Tensor &cand_points, const at::Tensor &cand_y,
+                   const at::Tensor &cand_sec, const at::Tensor &pts_out, const at::Tensor &y_out, const at::Tensor &sec_out, const at::Tensor &n_out,
+                   const OT &accepted, const OT &front_idx, const OT &hv_front, const OT &metrics) {
+  const Backend &b = backend(lib);
+  need(b.archive_merge, "truss_archive_merge");
+  TORCH_CHECK(pts_in.dim() == 3 && pts_in.size(2) == 4, "truss_mi355: pts_in must be [B, P, 4]");
+  const int64_t B = pts_in.size(0), P = pts_in.size(1), C = n_slots;
+  TORCH_CHECK(y_in.dim() == 3 && y_in.size(0) == B && y_in.size(1) == P, "truss_mi355: y_in must be [B, P, n_y]");
+  TORCH_CHECK(sec_in.dim() == 3 && sec_in.size(0) == B && sec_in.size(1) == P, "truss_mi355: sec_in must be [B, P, n_sec]");
+  const int64_t ny = y_in.size(2), ns = sec_in.size(2);
+  TORCH_CHECK(n_in.dim() == 1 && n_in.size(0) == B, "truss_mi355: n_in must be [B]");
+  TORCH_CHECK(C >= 0 && C <= INT32_MAX, "truss_mi355: n_slots must be >= 0");
+  TORCH_CHECK(!present(slot_row) || (slot_row->dim() == 2 && slot_row->size(0) == B && slot_row->size(1) == C), "truss_mi355: slot_row must be [B, n_slots]");
+  TORCH_CHECK(cand_points.dim() == 2 && cand_points.size(1) == 4, "truss_mi355: cand_points must be [R, 4]");
+  const int64_t R = cand_points.size(0);
+  TORCH_CHECK(cand_y.dim() == 2 && cand_y.size(0) == R && cand_y.size(1) == ny, "truss_mi355: cand_y must be [R, n_y] like y_in's rows");
+  TORCH_CHECK(cand_sec.dim() == 2 && cand_sec.size(0) == R && cand_sec.size(1) == ns, "truss_mi355: cand_sec must be [R, n_sec] like sec_in's rows");
+  TORCH_CHECK(pts_out.dim() == 3 && pts_out.size(0) == B && pts_out.size(2) == 4, "truss_mi355: pts_out must be [B, max_out, 4]");
+  const int64_t O = pts_out.size(1);
+  TORCH_CHECK(y_out.dim() == 3 && y_out.size(0) == B && y_out.size(1) == O && y_out.size(2) == ny, "truss_mi355: y_out must be [B, max_out, n_y]");
+  TORCH_CHECK(sec_out.dim() == 3 && sec_out.size(0) == B && sec_out.size(1) == O && sec_out.size(2) == ns, "truss_mi355: sec_out must be [B, max_out, n_sec]");
+  TORCH_CHECK(n_out.dim() == 1 && n_out.size(0) == B, "truss_mi355: n_out must be [B]");
+  TORCH_CHECK(!present(accepted) || (accepted->dim() == 2 && accepted->size(0) == B && accepted->size(1) == C), "truss_mi355: accepted must be [B, n_slots]");
+  TORCH_CHECK(!present(front_idx) || (front_idx->dim() == 2 && front_idx->size(0) == B && front_idx->size(1) == O), "truss_mi355: front_idx must be [B, max_out]");
+  TORCH_CHECK(!present(hv_front) || (hv_front->dim() == 1 && hv_front->size(0) == B), "truss_mi355: hv_front must be [B]");
+  TORCH_CHECK(!present(metrics) || (metrics->dim() == 2 && metrics->size(0) == B && metrics->size(1) == 5), "truss_mi355: metrics must be [B, 5]");
+  TORCH_CHECK(B <= INT32_MAX && P <= INT32_MAX && O <= INT32_MAX && R <= INT32_MAX && ny <= INT32_MAX && ns <= INT32_MAX && max_front >= INT32_MIN &&
+                  max_front <= INT32_MAX, "truss_mi355: archive_merge: a size does not fit 32 bits");
+  truss_archive_args_t a{};
+  a.struct_size = sizeof(truss_archive_args_t);
+  a.n_envs = (int32_t)B;
+  a.max_points = (int32_t)P;
+  a.n_slots = (int32_t)C;
+  a.max_front = (int32_t)max_front;
+  a.max_out = (int32_t)O;
+  a.n_y = (int32_t)ny;
+  a.n_sec = (int32_t)ns;
+  a.n_cand_rows = (int32_t)R;
+  a.pts_in = ptr<const double>(b, pts_in, at::kDouble, "pts_in");
+  a.n_in = ptr<const int32_t>(b, n_in, at::kInt, "n_in");
+  a.y_in = ptr<const float>(b, y_in, at::kFloat, "y_in");
+  a.sec_in = ptr<const int32_t>(b, sec_in, at::kInt, "sec_in");
+  a.slot_row = ptr<const int32_t>(b, slot_row, at::kInt, "slot_row");
+  a.cand_points = ptr<const double>(b, cand_points, at::kDouble, "cand_points");
+  a.cand_y = ptr<const float>(b, cand_y, at::kFloat, "cand_y");
+  a.cand_sec = ptr<const int32_t>(b, cand_sec, at::kInt, "cand_sec");
+  a.pts_out = ptr<double>(b, pts_out, at::kDouble, "pts_out");
+  a.y_out = ptr<float>(b, y_out, at::kFloat, "y_out");
+  a.sec_out = ptr<int32_t>(b, sec_out, at::kInt, "sec_out");
+  a.n_out = ptr<int32_t>(b, n_out, at::kInt, "n_out");
+  a.accepted = ptr<uint8_t>(b, accepted, at::kByte, "accepted");
+  a.front_idx = ptr<int32_t>(b, front_idx, at::kInt, "front_idx");
+  a.hv_front = ptr<double>(b, hv_front, at::kDouble, "hv_front");
+  a.metrics = ptr<double>(b, metrics, at::kDouble, "metrics");
+  check_rc(b, b.archive_merge(&a, (void *)stream), "truss_archive_merge");
+}
+
 // every operator on meta tensors (tracing): nothing to compute, the schema says what is mutated
 void noop_boxed(const c10::OperatorHandle &op, torch::jit::Stack *s) { torch::jit::drop(*s, op.schema().arguments().size()); }
 
@@ -556,6 +617,9 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("replay_gather(int lib, int stream, Tensor[] ring, Tensor(a!)[] out, Tensor?[] nbr, Tensor idx, int capacity) -> ()");
   m.def("reward(int lib, int stream, int max_front, Tensor front_no, Tensor n_front_no, Tensor pf_hv, Tensor n_pf_hv, Tensor parent, Tensor points, "
         "Tensor ref_points, Tensor n_pf, Tensor(a!) R, Tensor(b!) G_U, Tensor(c!) xmax, Tensor(d!) ymax, Tensor(e!)? parts) -> ()");
+  m.def("archive_merge(int lib, int stream, int max_front, int n_slots, Tensor pts_in, Tensor n_in, Tensor y_in, Tensor sec_in, Tensor? slot_row, "
+        "Tensor cand_points, Tensor cand_y, Tensor cand_sec, Tensor(a!) pts_out, Tensor(b!) y_out, Tensor(c!) sec_out, Tensor(d!) n_out, "
+        "Tensor(e!)? accepted, Tensor(f!)? front_idx, Tensor(g!)? hv_front, Tensor(h!)? metrics) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

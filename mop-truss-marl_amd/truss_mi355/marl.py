@@ -570,8 +570,13 @@ class BatchedMARL:
     def __init__(self, topo: TrussTopology, n_envs: int, maddpg, *, max_front: int | None = None, lib=None, device=None,
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
                  pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None,
-                 level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None):
-        """reward_path: how a game step computes the difference reward of a chunk of pairs -- "torch" (three `truss_front` launches plus
+                 level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None,
+                 archive_path: str | None = None):
+        """archive_path: how a game step updates the archives -- "torch" (candidate buffers, one `truss_front` launch and gathers by
+        framework operators, the default) or "hip" (one `truss_archive_merge` launch per chunk, per step in the design game; needs a
+        library with that entry; the archive then lives in two sets of buffers that swap roles); None: "hip" if the environment has
+        TRUSS_ARCHIVE=hip, else "torch".  Both play the same game, bit for bit.
+        reward_path: how a game step computes the difference reward of a chunk of pairs -- "torch" (three `truss_front` launches plus
         element-wise operators, the default) or "hip" (one `truss_reward` launch; needs max_front + 3 <= 64 and a library with that
         entry); None: "hip" if the environment has TRUSS_REWARD=hip, else "torch".
         replay_storage: "dense" (the default) or "compact" (`DeviceReplay`: adjacencies stored through the neighbour tables, one
@@ -628,6 +633,18 @@ class BatchedMARL:
             if self.P + 3 > 64:
                 raise ValueError(f"reward_path='hip': max_front {self.P} + 3 new points exceed the 64 rows of a wave (truss_reward)")
         self.reward_path = reward_path
+        if archive_path is None:
+            archive_path = "hip" if os.environ.get("TRUSS_ARCHIVE", "torch") == "hip" else "torch"
+        if archive_path not in ("torch", "hip"):
+            raise ValueError(f"archive_path must be 'torch' or 'hip', got {archive_path!r}")
+        if archive_path == "hip":
+            if not self.lib.has_archive:
+                raise ValueError(f"archive_path='hip': {self.lib.path} has no truss_archive_merge")
+            if self.P + 3 * self.Gm > _lib.ARCHIVE_MAXROWS:
+                raise ValueError(f"archive_path='hip': max_front {self.P} + {3 * self.Gm} candidate slots exceed the "
+                                 f"{_lib.ARCHIVE_MAXROWS} rows of truss_archive_merge")
+        self.archive_path = archive_path
+        self._arch_spare = None        # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
         if self.device.type == "cuda":
             import truss2D_RL
             truss2D_RL.set_level_backward(_level_backward_hook(self.lib) if level_backward == "hip" else None, "cuda")
@@ -914,40 +931,50 @@ class BatchedMARL:
                 # ---- archive update (D1): front of (working archive + the feasible candidates of this chunk's members) ----
                 C3 = 3 * Gm
                 slot = ((ms - g0) * 3)[:, None] + self._const("ar3", lambda: torch.arange(3, device=dev)[None, :])   # [K, 3] candidate slot of (pair, agent)
-                candP = self._const("candP", lambda: torch.tensor([0.0, 0.0, 2.0, 0.0], dtype=torch.float64, device=dev).expand(B, C3, 4)).clone()
-                #                                                                               (empty slot = infeasible row: [0, 0, 2, 0])
-                candY = torch.zeros((B, C3, N), dtype=torch.float32, device=dev)
-                candS = torch.zeros((B, C3, E), dtype=torch.int32, device=dev)
-                pmark = points.clone()
-                pmark[:, :, 2] = torch.where(ok, pmark[:, :, 2], 2.0)
-                candP[idx[:, None], slot] = pmark
-                candY[idx[:, None], slot] = cand_y
-                candS[idx[:, None], slot] = cand_sec
-                wp, wy, ws, wn = self.pts, self.arch_y, self.arch_sec, self.n
-                origp = torch.cat([wp, candP], dim=1)
-                allp = origp.clone()
-                dead = arP[None, :] >= wn[:, None]
-                allp[:, :P, 2] = torch.where(dead, 2.0, allp[:, :P, 2])                          # infeasible marker
-                fr = RW.front_hv(allp, self._const("full_front", lambda: torch.full((B,), P + C3, dtype=torch.int32, device=dev)), None,
-                                 max_front=P, lib=self.lib)
-                fidx = fr["front_idx"][:, :P].long()
-                take = fidx.clamp(min=0)
-                ally = torch.cat([wy, candY], dim=1)
-                alls = torch.cat([ws, candS], dim=1)
-                rows = self._const("rows", lambda: torch.arange(B, device=dev)[:, None])
-                live = (fidx >= 0)[:, :, None]
-                newp = torch.where(live, origp[rows, take], 0.0)
-                newp[:, :, 0:2].clamp_(max=1.0)                                                   # :434-436
-                self.pts = newp
-                self.arch_y = torch.where(live, ally[rows, take], 0.0)
-                self.arch_sec = torch.where(live, alls[rows, take], 0)
-                self.n = fr["n_front"].clamp(max=P)                                           # (int32 already)
+                if self.archive_path == "hip":
+                    # one launch: the candidates are handed over as they lie (agent-major rows a K + k of the candidate env's tensors)
+                    # through a [B, C3] table of rows, -1 = empty slot
+                    slot_row = torch.full((B, C3), -1, dtype=torch.int32, device=dev)
+                    slot_row[idx[:, None], slot] = (self._const("ar3", lambda: torch.arange(3, device=dev)[None, :]) * K + ark[:, None]).int()
+                    acc = self._merge_archive(eC.point[:3 * K].double(), eC.y[:3 * K], eC.sec[:3 * K], slot_row, C3, accepted=train)
+                else:
+                    candP = self._const("candP", lambda: torch.tensor([0.0, 0.0, 2.0, 0.0], dtype=torch.float64, device=dev).expand(B, C3, 4)).clone()
+                    #                                                                               (empty slot = infeasible row: [0, 0, 2, 0])
+                    candY = torch.zeros((B, C3, N), dtype=torch.float32, device=dev)
+                    candS = torch.zeros((B, C3, E), dtype=torch.int32, device=dev)
+                    pmark = points.clone()
+                    pmark[:, :, 2] = torch.where(ok, pmark[:, :, 2], 2.0)
+                    candP[idx[:, None], slot] = pmark
+                    candY[idx[:, None], slot] = cand_y
+                    candS[idx[:, None], slot] = cand_sec
+                    wp, wy, ws, wn = self.pts, self.arch_y, self.arch_sec, self.n
+                    origp = torch.cat([wp, candP], dim=1)
+                    allp = origp.clone()
+                    dead = arP[None, :] >= wn[:, None]
+                    allp[:, :P, 2] = torch.where(dead, 2.0, allp[:, :P, 2])                          # infeasible marker
+                    fr = RW.front_hv(allp, self._const("full_front", lambda: torch.full((B,), P + C3, dtype=torch.int32, device=dev)), None,
+                                     max_front=P, lib=self.lib)
+                    fidx = fr["front_idx"][:, :P].long()
+                    take = fidx.clamp(min=0)
+                    ally = torch.cat([wy, candY], dim=1)
+                    alls = torch.cat([ws, candS], dim=1)
+                    rows = self._const("rows", lambda: torch.arange(B, device=dev)[:, None])
+                    live = (fidx >= 0)[:, :, None]
+                    newp = torch.where(live, origp[rows, take], 0.0)
+                    newp[:, :, 0:2].clamp_(max=1.0)                                                   # :434-436
+                    self.pts = newp
+                    self.arch_y = torch.where(live, ally[rows, take], 0.0)
+                    self.arch_sec = torch.where(live, alls[rows, take], 0)
+                    self.n = fr["n_front"].clamp(max=P)                                           # (int32 already)
                 tk = self._tick("archive update", tk)
                 # ---- replay (D2): one row per pair with an accepted candidate ----
                 if train:
-                    infront = torch.zeros((B, P + C3), dtype=torch.bool, device=dev)
-                    infront.scatter_(1, take, live[:, :, 0])
-                    accepted = infront[idx[:, None], P + slot] & ok                          # [K, 3]
+                    if self.archive_path == "hip":
+                        accepted = acc[idx[:, None], slot].bool()                            # [K, 3]: one gather from the kernel's flags
+                    else:
+                        infront = torch.zeros((B, P + C3), dtype=torch.bool, device=dev)
+                        infront.scatter_(1, take, live[:, :, 0])
+                        accepted = infront[idx[:, None], P + slot] & ok                      # [K, 3]
                     first_ok = torch.argmax(ok.int(), dim=1)                                   # D4
                     # next state of agent a = its own candidate where that is feasible, else the first feasible one (D4): the rows are
                     # picked from the agent-major candidate tensors inside `add`, for the accepted pairs only
@@ -985,6 +1012,16 @@ class BatchedMARL:
         master…:424-428, 680): the archive is left as it was and `self.final` = dict(points [B, 4P, 4] (objectives clipped to <= 1
         like the archive's, :683-686), y [B, 4P, N], sec [B, 4P, E], n [B], hv [B], metrics [B, 5]), rows beyond n zero."""
         B, P, dev = self.B, self.P, self.device
+        if self.archive_path == "hip":          # one launch on the dense step-wide buffers: slot c of env b is row b 3P + c
+            N, E = candY.shape[2], candS.shape[2]
+            cand = (candP.view(B * 3 * P, 4), candY.view(B * 3 * P, N), candS.view(B * 3 * P, E))
+            if not final:
+                self._merge_archive(*cand, None, 3 * P, accepted=False)
+                return None
+            fr = RW.archive_merge(self.pts.contiguous(), self.n, self.arch_y.contiguous(), self.arch_sec.contiguous(), *cand, None, n_slots=3 * P,
+                                  max_front=0, max_out=4 * P, accepted=False, extras=True, lib=self.lib)
+            self.final = dict(points=fr["points"], y=fr["y"], sec=fr["sec"], n=fr["n"], hv=fr["hv_front"], metrics=fr["metrics"])
+            return self.final
         arP = self._const("arP", lambda: torch.arange(P, device=dev))
         origp = torch.cat([self.pts, candP], dim=1)
         allp = origp.clone()
@@ -1004,6 +1041,20 @@ class BatchedMARL:
         else:
             self.pts, self.arch_y, self.arch_sec, self.n = newp, newy, news, fr["n_front"]
         return self.final if final else None
+
+    def _merge_archive(self, cand_points, cand_y, cand_sec, slot_row, n_slots, accepted):
+        """archive_path="hip": one `truss_archive_merge` launch from the current archive buffers into the spare set, truncated to
+        max_front; the two sets then swap roles (the entry refuses to write over its inputs).  Returns accepted [B, n_slots] uint8
+        (None unless asked for)."""
+        P = self.P
+        cur = dict(points=self.pts.contiguous(), y=self.arch_y.contiguous(), sec=self.arch_sec.contiguous(), n=self.n)
+        if self._arch_spare is None:
+            self._arch_spare = {k: torch.empty_like(v) for k, v in cur.items()}
+        res = RW.archive_merge(cur["points"], cur["n"], cur["y"], cur["sec"], cand_points, cand_y, cand_sec, slot_row, n_slots=n_slots,
+                               max_front=P, max_out=P, accepted=accepted, out=self._arch_spare, lib=self.lib)
+        self.pts, self.arch_y, self.arch_sec, self.n = res["points"], res["y"], res["sec"], res["n"]
+        self._arch_spare = cur
+        return res.get("accepted")
 
     def design_episode(self, end_step: int = 500, explore: bool = True):
         """One episode of the design game (game="test") from the state `reset` left: game steps game_step .. end_step, the last

@@ -43,6 +43,56 @@ def front_hv(points, n_points, ref_points=None, max_front=0, lib=None, stream=No
     return out
 
 
+def archive_merge(pts_in, n_in, y_in, sec_in, cand_points, cand_y, cand_sec, slot_row=None, n_slots=None, max_front=0, max_out=None,
+                  accepted=True, extras=False, out=None, lib=None, stream=None):
+    """The archive update of a game step as one `truss_archive_merge` launch (include/truss_mi355.h, csrc/truss_archive.h): per env the
+    cull of `truss_front` over the P archive rows (rows >= n_in dead) and C candidate slots, truncated to max_front (0: not at all),
+    and the surviving rows, designs and flags gathered in front order.
+
+    pts_in [B,P,4] float64, n_in [B] int32, y_in [B,P,n_y] float32, sec_in [B,P,n_sec] int32      the archive
+    cand_points [R,4] float64, cand_y [R,n_y] float32, cand_sec [R,n_sec] int32                  the candidates as they lie
+    slot_row [B,C] int32: row of the candidate arrays in slot c of env b, -1 = empty; None: slot c of env b is row b C + c
+                          (n_slots = C is needed then)
+    max_out    rows per env of the outputs (default: max_front when truncating, P + C otherwise)
+    out        dict of preallocated outputs (any of the keys below) to write into instead of new tensors; they must not overlap
+               the inputs (the archive is not updated in place)
+    Returns dict(points [B,max_out,4], y [B,max_out,n_y], sec [B,max_out,n_sec], n [B] int32, accepted [B,C] uint8 (accepted=True),
+    and with extras=True front_idx [B,max_out] int32, hv_front [B], metrics [B,5]); rows >= n are zeros."""
+    lib = lib or _lib.load()
+    if not lib.has_archive:
+        raise _lib.TrussError(f"{lib.path} has no truss_archive_merge (the fused archive update)")
+    B, P = pts_in.shape[0], pts_in.shape[1]
+    if slot_row is not None:
+        C = slot_row.shape[1]
+        if n_slots is not None and int(n_slots) != C:
+            raise ValueError(f"n_slots {n_slots} does not match slot_row [B, {C}]")
+    elif n_slots is None:
+        raise ValueError("archive_merge without slot_row needs n_slots (slot c of env b is candidate row b n_slots + c)")
+    else:
+        C = int(n_slots)
+    if P + C > _lib.ARCHIVE_MAXROWS:
+        raise ValueError(f"the fused archive update takes at most {_lib.ARCHIVE_MAXROWS} rows per env, got P + C = {P} + {C}")
+    max_front = int(max_front)
+    if max_out is None:
+        max_out = max_front if max_front >= 2 else P + C
+    O, dev = int(max_out), pts_in.device
+    out = dict(out or {})
+    new = lambda key, shape, dt: out[key] if key in out else torch.empty(shape, dtype=dt, device=dev)
+    res = dict(points=new("points", (B, O, 4), torch.float64), y=new("y", (B, O, y_in.shape[2]), torch.float32),
+               sec=new("sec", (B, O, sec_in.shape[2]), torch.int32), n=new("n", (B,), torch.int32))
+    if accepted:
+        res["accepted"] = new("accepted", (B, C), torch.uint8)
+    if extras:
+        res.update(front_idx=new("front_idx", (B, O), torch.int32), hv_front=new("hv_front", (B,), torch.float64),
+                   metrics=new("metrics", (B, 5), torch.float64))
+    from . import ops
+    stream_i = ops.stream_of(dev) if stream is None else int(getattr(stream, "value", stream) or 0)
+    ops.call(ops.namespace().archive_merge, ops.bind(lib), stream_i, max_front, C, pts_in, n_in, y_in, sec_in, slot_row, cand_points, cand_y,
+             cand_sec, res["points"], res["y"], res["sec"], res["n"], res.get("accepted"), res.get("front_idx"), res.get("hv_front"),
+             res.get("metrics"))
+    return res
+
+
 def _append(base, n_base, extra, use):
     """rows of `extra` [B,K,4] with use[B,K] appended (in order) behind the first n_base rows of base [B,P,4]."""
     B, P, _ = base.shape
