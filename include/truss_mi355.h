@@ -426,6 +426,39 @@ typedef struct truss_gcn_layer_args {
 
 int truss_gcn_layer(const truss_gcn_layer_args_t *args, void *stream);
 
+/* The same layer with a CONSUMER of its output in the epilogue of the same launch, for the three activations of the actor's
+ * inference that are written to HBM only to be read back once (truss2D_RL.py:86-120).  With V = act(A (X W^T) + bias), the layer's
+ * output:
+ *   TRUSS_GCN_EPI_HEAD  out2 = act2(A2 (V W2^T) + bias2): a second, narrow GCN layer (an action head: gcn_l3_x + gcn_l4_x).
+ *       w2   [c2][c_out] float32 as it lies in nn.Linear.weight, 1 <= c2 <= 8; bias2 [c2] or NULL; act2 as act
+ *       adj2 / a2_batch_stride / nbr2 / k_nbr2: the head's own adjacency over the same n_nodes, as adj / a_batch_stride / nbr / k_nbr
+ *       out2 [n_batch][n_nodes][c2], rows out2_row_stride floats apart (0 = c2)
+ *   TRUSS_GCN_EPI_POOL  pool[b][c] = sum over ALL n_nodes rows n of V[b][n][c] (GlobalSumPool: gcn_l1_4 over the Pareto graph)
+ *       pool [n_batch][c_out], rows pool_row_stride floats apart (0 = c_out)
+ * `layer` is what truss_gcn_layer takes (both products), except that layer->out may be NULL -- V is then never written, which is
+ * the point -- and layer->accumulate must be 0.  out2 / pool must not overlap x, out or each other.  One owner per output element,
+ * fixed summation order, no atomics: results are bitwise reproducible.  Neither allocates nor synchronises; capturable.
+ * Optional entry of ABI version 3 (a library may lack it). */
+#define TRUSS_GCN_EPI_HEAD 1
+#define TRUSS_GCN_EPI_POOL 2
+typedef struct truss_gcn_epilogue {
+  uint32_t struct_size;
+  int32_t kind;
+  /* HEAD */
+  const float *w2;
+  const float *bias2;
+  const float *adj2;
+  int64_t a2_batch_stride;
+  const int16_t *nbr2;
+  int32_t k_nbr2, c2, act2;
+  float *out2;
+  int64_t out2_row_stride;
+  /* POOL */
+  float *pool;
+  int64_t pool_row_stride;
+} truss_gcn_epilogue_t;
+int truss_gcn_layer_fused(const truss_gcn_layer_args_t *layer, const truss_gcn_epilogue_t *epi, void *stream);
+
 /* A whole LEVEL of GCN layers in one launch: layers[i] as for truss_gcn_layer, for n_layers layers that do not depend on each other
  * -- the layers of one depth of the reference's actor / critic graphs (truss2D_RL.py:86-103, 116-133), of one network or of
  * several.  replaces: the forward passes of the MADDPG update (truss2D_RL.py:561-629: 19 network passes of 13 / 21 GCN layers at

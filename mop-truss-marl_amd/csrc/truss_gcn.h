@@ -60,6 +60,45 @@ static inline int tb_gcn_bf16x3_check(const truss_gcn_layer_args_t *a) {
   return TRUSS_OK;
 }
 
+// [p, p + n floats) and [q, q + m floats) share a byte
+static inline bool tb_gcn_overlap(const float *p, int64_t n, const float *q, int64_t m) {
+  return p && q && n > 0 && m > 0 && (uintptr_t)p < (uintptr_t)(q + m) && (uintptr_t)q < (uintptr_t)(p + n);
+}
+
+// The argument blocks of truss_gcn_layer_fused: the epilogue's own fields, then the layer through tb_gcn_layer_check as truss_gcn_layer
+// takes it -- except that `out` may be NULL (the check then sees the epilogue's result in its place) and nothing accumulates.
+static inline int tb_gcn_fused_check(const truss_gcn_layer_args_t *a, const truss_gcn_epilogue_t *e) {
+  const char *what = "truss_gcn_layer_fused";
+  auto fail = [what](int code, const std::string &msg) { return tb_fail(code, what + msg); };
+  if (a->struct_size != sizeof(truss_gcn_layer_args_t)) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer_args_t size mismatch (ABI)");
+  if (e->struct_size != sizeof(truss_gcn_epilogue_t)) return tb_fail(TRUSS_EINVAL, "truss_gcn_epilogue_t size mismatch (ABI)");
+  const bool head = e->kind == TRUSS_GCN_EPI_HEAD;
+  if (!head && e->kind != TRUSS_GCN_EPI_POOL) return fail(TRUSS_EINVAL, ": unknown epilogue kind");
+  if (head) {
+    if (!e->w2 || !e->adj2 || !e->out2) return fail(TRUSS_EINVAL, ": a required pointer of the head is NULL");
+    if (e->c2 < 1 || e->c2 > 8 || e->act2 < 0 || e->act2 > 2) return fail(TRUSS_EINVAL, ": c2 1..8, act2 0..2");
+  } else if (!e->pool) {
+    return fail(TRUSS_EINVAL, ": pool is NULL");
+  }
+  if (a->accumulate) return fail(TRUSS_EINVAL, ": no accumulation into out");
+  float *res = head ? e->out2 : e->pool;
+  truss_gcn_layer_args_t c = *a;
+  if (!c.out) c.out = res;
+  if (int rc = tb_gcn_layer_check(&c, what, 256, 0, false)) return rc;
+  if (head && (e->nbr2 ? (e->k_nbr2 < 1 || e->k_nbr2 > 16) : a->n_nodes > 64))
+    return fail(TRUSS_EUNSUPPORTED, ": head: a sparsity pattern of 1..16 terms per row, or a dense adjacency of at most 64 nodes");
+  if (a->n_batch == 0) return TRUSS_OK;
+  const int64_t R = (int64_t)a->n_batch * a->n_nodes;
+  const int64_t nx = (R - 1) * (a->x_row_stride ? a->x_row_stride : a->k_in) + a->k_in;
+  const int64_t no = (R - 1) * (a->out_row_stride ? a->out_row_stride : a->c_out) + a->c_out;
+  const int64_t n2 = (R - 1) * (e->out2_row_stride ? e->out2_row_stride : e->c2) + e->c2;
+  const int64_t np = ((int64_t)a->n_batch - 1) * (e->pool_row_stride ? e->pool_row_stride : a->c_out) + a->c_out;
+  const int64_t nr = head ? n2 : np;
+  if (tb_gcn_overlap(res, nr, a->x, nx) || tb_gcn_overlap(res, nr, a->out, no) || tb_gcn_overlap(e->out2, n2, e->pool, np))
+    return fail(TRUSS_EINVAL, ": out2 / pool must not overlap x, out or each other");
+  return TRUSS_OK;
+}
+
 #ifdef __HIPCC__
 typedef float tg_f4 __attribute__((ext_vector_type(4)));
 typedef float tg_f16 __attribute__((ext_vector_type(16)));
@@ -85,6 +124,179 @@ struct GcnLayerDev {
 // vmcnt(0), i.e. for the global loads of the slab after next that are meant to stay in flight across the barrier.
 __device__ __forceinline__ void tg_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// ---- a consumer of the layer's output in the epilogue of the same launch (truss_gcn_layer_fused) ----
+// The epilogue mode is a template parameter of both kernels; TG_EPI_NONE is the layer as truss_gcn_layer launches it, with the
+// argument block it has always had.  The other two hand the output V = act(acc + bias) over through LDS, one 32-column block
+// at a time (MT x 32 floats in the LDS the slab loop has finished with), to threads that own whole output elements:
+//   HEAD  thread (row, 16-column half) extends its partial sums of h2 = V W2^T, c2 <= 8 of them, block after block; the two
+//         halves are added, h2 [MT][8] goes to LDS, and thread (row, four of the c2 columns) forms act2(sum_t A2[r][t] h2[row(r, t)]
+//         + b2) -- through LDS for every shape, since a graph's rows lie in several waves;
+//   POOL  thread (graph, column) adds the N rows of its graph in row order and writes pool[b][c].
+// One owner per element, a fixed order of every sum, no atomics.  V itself is written to `out` only when out != NULL.
+#define TG_EPI_NONE 0
+#define TG_EPI_HEAD 1            // = TRUSS_GCN_EPI_HEAD
+#define TG_EPI_POOL 2            // = TRUSS_GCN_EPI_POOL
+static_assert(TG_EPI_HEAD == TRUSS_GCN_EPI_HEAD && TG_EPI_POOL == TRUSS_GCN_EPI_POOL, "epilogue kinds of the C ABI");
+#define TG_VLD 36                // floats per LDS row of a 32-column block of V (32 + 4 padding: rows 144 bytes apart)
+#define TG_W2LD 224              // floats per LDS row of W2 (c_out padded to the 7 column blocks, zeros)
+
+struct GcnFusedDev : GcnLayerDev {
+  const float *w2, *bias2, *adj2;
+  const int16_t *nbr2;
+  float *out2, *pool;
+  long a2_stride, out2_stride, pool_stride;
+  int c2, act2, Kn2;
+};
+template <int EPI> struct TgArgs { typedef GcnFusedDev type; };
+template <> struct TgArgs<TG_EPI_NONE> { typedef GcnLayerDev type; };
+
+static size_t tg_epi_lds_bytes(int NW) { return sizeof(float) * ((size_t)32 * NW * (TG_VLD + 8) + 8 * TG_W2LD); }
+
+// All barriers of the epilogue are at the top level of this function (the loop over the column blocks is unrolled), and the kernels
+// call it outside every branch: every wave of the workgroup passes every one of them.
+template <int NW, int CB, int EPI>
+__device__ __forceinline__ void tg_fused_epilogue(const GcnFusedDev &P, const tg_f16 (&acc)[CB], char *smem, int rows, long row0, int g0, int ng) {
+  constexpr int MT = 32 * NW, NT = 64 * NW;
+  float *sV = (float *)smem;                               // [MT][TG_VLD]  one 32-column block of V
+  float *sW2 = sV + MT * TG_VLD;                           // [8][TG_W2LD]  W2, zero rows / columns past c2 / c_out
+  float *sH = sW2 + 8 * TG_W2LD;                           // [MT][8]       h2 = V W2^T
+  // (opaque to the optimiser: the row / graph / node numbers below are worked out again here.  Shared with the copies from before
+  // the slab loop, they would stay live across it, and the float32 loop has no register to spare.)
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, wave = tid >> 6;
+  const int N = P.N, C = P.C, c2 = P.c2, Kn2 = P.Kn2;
+  // The last iterations of the slab loops still post slabs past the end of K (register -> LDS copies, LDS-DMA): they must have
+  // landed in EVERY wave before the first write of the epilogue reuses that LDS.
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+
+  // item of this thread: row ar, half ah (HEAD: columns 16 ah .. of every block, then the head's columns 4 ah ..)
+  const int ar = tid >> 1, ah = tid & 1;
+  const int ag = ar / N, an = ar - ag * N;
+  const bool alive = ar < rows;
+  const bool kreg2 = Kn2 <= TG_KREG;                       // uniform
+  float cf2[TG_KREG], hs[8];
+  uint32_t cj2[(TG_KREG + 3) / 4] = {};
+#pragma unroll
+  for (int t = 0; t < TG_KREG; ++t) cf2[t] = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) hs[j] = 0.0f;
+  if constexpr (EPI == TG_EPI_HEAD) {
+    for (int i = tid; i < 8 * TG_W2LD; i += NT) {
+      const int j = i / TG_W2LD, c = i - j * TG_W2LD;
+      const bool ok = j < c2 && c < C;
+      const float w = P.w2[ok ? j * C + c : 0];
+      sW2[i] = ok ? w : 0.0f;
+    }
+    if (kreg2) {                                           // A2's terms of this row: in flight over the rounds below
+      int jj[TG_KREG];
+#pragma unroll
+      for (int t = 0; t < TG_KREG; ++t) {
+        const bool use = alive && t < Kn2;
+        jj[t] = P.nbr2 ? (int)P.nbr2[use ? an * Kn2 + t : 0] : t;
+        jj[t] = use ? jj[t] : -1;
+      }
+#pragma unroll
+      for (int t = 0; t < TG_KREG; ++t) {
+        const int j = jj[t];
+        const float c = P.adj2[j < 0 ? 0 : (long)(g0 + ag) * P.a2_stride + (long)an * N + j];
+        cf2[t] = j < 0 ? 0.0f : c;
+        cj2[t >> 2] |= (uint32_t)(j < 0 ? 0 : j) << (8 * (t & 3));
+      }
+    }
+  }
+
+  const int act = P.act;
+  const int rbase = wave * 32 + 4 * (lane >> 5);            // row of accumulator register 0; register i: + 8 (i / 4) + i % 4
+  const long ostride = P.out_stride;
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) {
+    const int col = cb * 32 + (lane & 31);
+    const bool colok = col < C;
+    const float bc = (P.bias && colok) ? P.bias[col] : 0.0f;
+    float *po = P.out + (row0 + rbase) * ostride + (colok ? col : 0);
+    const bool store = P.out != nullptr && colok;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int dr = 8 * (i >> 2) + (i & 3);
+      float v = acc[cb][i] + bc;
+      if (act == 1) v = fmaxf(v, 0.0f);
+      else if (act == 2) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+      sV[(rbase + dr) * TG_VLD + (lane & 31)] = colok ? v : 0.0f;
+      if (store && rbase + dr < rows) po[dr * ostride] = v;
+    }
+    tg_lds_barrier();                                       // the block (and, first round, W2) is in LDS
+    if constexpr (EPI == TG_EPI_HEAD) {
+      if (alive) {
+        const float *pv = sV + ar * TG_VLD + ah * 16;
+        const float *pw = sW2 + cb * 32 + ah * 16;
+        tg_f4 v4[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v4[q] = *(const tg_f4 *)(pv + 4 * q);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (j < c2) {                                     // uniform
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const tg_f4 w4 = *(const tg_f4 *)(pw + j * TG_W2LD + 4 * q);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) hs[j] += v4[q][e] * w4[e];
+            }
+          }
+        }
+      }
+    } else {
+      for (int it = tid; it < ng * 32; it += NT) {          // (graph, column) of the block
+        const int g = it >> 5, c = it & 31;
+        if (cb * 32 + c < C) {
+          const float *pv = sV + (g * N) * TG_VLD + c;
+          float s = 0.0f;
+          for (int n = 0; n < N; ++n) s += pv[n * TG_VLD];
+          P.pool[(long)(g0 + g) * P.pool_stride + cb * 32 + c] = s;
+        }
+      }
+    }
+    tg_lds_barrier();                                       // everybody is done with the block
+  }
+
+  if constexpr (EPI == TG_EPI_HEAD) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) hs[j] += __shfl_xor(hs[j], 1);          // the other half's 16 columns of every block
+    if (alive) {
+      const tg_f4 lo = {hs[0], hs[1], hs[2], hs[3]}, hi = {hs[4], hs[5], hs[6], hs[7]};
+      *(tg_f4 *)(sH + ar * 8 + ah * 4) = ah ? hi : lo;
+    }
+    tg_lds_barrier();                                       // h2 of every live row is in LDS
+    if (alive && ah * 4 < c2) {
+      const float *hb = sH + (ag * N) * 8 + ah * 4;
+      tg_f4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (kreg2) {
+#pragma unroll
+        for (int t = 0; t < TG_KREG; ++t)
+          s += cf2[t] * *(const tg_f4 *)(hb + (int)((cj2[t >> 2] >> (8 * (t & 3))) & 255u) * 8);
+      } else {
+        for (int t = 0; t < Kn2; ++t) {
+          const int j = P.nbr2 ? (int)P.nbr2[an * Kn2 + t] : t;
+          if (j < 0) continue;
+          s += P.adj2[(long)(g0 + ag) * P.a2_stride + (long)an * N + j] * *(const tg_f4 *)(hb + j * 8);
+        }
+      }
+      const int act2 = P.act2;
+      float *po2 = P.out2 + (row0 + ar) * P.out2_stride;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int j = ah * 4 + q;
+        if (j < c2) {
+          float v = s[q] + (P.bias2 ? P.bias2[j] : 0.0f);
+          if (act2 == 1) v = fmaxf(v, 0.0f);
+          else if (act2 == 2) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+          po2[j] = v;
+        }
+      }
+    }
+  }
+}
+
 #ifdef TRUSS_GCN_STAMPS   // diagnostic build: cycles of the slab loop's sections, block 0 / wave 0 (tools/gcn_stamps.py)
 __device__ unsigned long long g_gcn_stamps[8];
 #define TG_T(v) unsigned long long v = clock64()
@@ -94,8 +306,8 @@ __device__ unsigned long long g_gcn_stamps[8];
 
 // VEC: x and w are 16-byte aligned with k_in % 4 == 0 -- every 4-float chunk of a slab is either whole or past the end, so the loads
 // are branch-free 16-byte loads from clamped addresses; otherwise (the 13-feature input layers) element-wise guarded loads.
-template <int NW, int CB, bool VEC>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void truss_gcn_layer_kernel(const GcnLayerDev P) {
+template <int NW, int CB, bool VEC, int EPI = TG_EPI_NONE>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void truss_gcn_layer_kernel(const typename TgArgs<EPI>::type P) {
   constexpr int MT = 32 * NW, NT = 64 * NW, WROWS = 32 * CB;
   extern __shared__ __attribute__((aligned(16))) char tg_smem[];
   float *sXraw = (float *)tg_smem;                         // [MT][TG_LD]       raw input rows of a slab
@@ -349,6 +561,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
     }
   }
 
+  if constexpr (EPI != TG_EPI_NONE) {                      // a consumer of the output in the same launch; its barriers are inside
+    tg_fused_epilogue<NW, CB, EPI>(P, acc, tg_smem, rows, row0, g0, ng);
+    return;
+  }
+
   // ---- epilogue: accumulator register i of a lane = row 8 (i / 4) + 4 (l / 32) + i % 4, column l % 32 of the 32 x 32 block.
   // Per column block: (accumulate: the 16 old values, from clamped addresses, in flight together) -> bias, activation -> 16
   // predicated stores; 32 lanes write 128 contiguous bytes of a row.  `act` / `accumulate` are uniform.
@@ -439,8 +656,8 @@ typedef __attribute__((address_space(1))) const void tg_glob_void;
 
 // KT: neighbourhood terms per row that are gathered (6: the grid trusses -- a node joins at most five others; 9: any pattern the
 // register path takes).  Terms past k_nbr have coefficient 0, but every one of them is two 16-byte LDS reads per slab and thread.
-template <int NW, int KT>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void truss_gcn_layer_bf3_kernel(const GcnLayerDev P, const uint16_t *__restrict__ ws, int KP) {
+template <int NW, int KT, int EPI = TG_EPI_NONE>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void truss_gcn_layer_bf3_kernel(const typename TgArgs<EPI>::type P, const uint16_t *__restrict__ ws, int KP) {
   constexpr int MT = 32 * NW, NT = 64 * NW, CB = 7, WROWS = 32 * CB;
   static_assert(WROWS == TG_CP, "split-weight image rows");
   extern __shared__ __attribute__((aligned(16))) char tg_smem[];
@@ -605,6 +822,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
   }
 #endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // no LDS-DMA may still be in flight when the workgroup ends
+  if constexpr (EPI != TG_EPI_NONE) {
+    tg_fused_epilogue<NW, CB, EPI>(P, acc, tg_smem, rows, row0, g0, ng);
+    return;
+  }
 
   const int act = P.act;
   const bool accum = P.accumulate != 0;
@@ -705,6 +926,66 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
   else { if (vec) TG_LAUNCH(8, 1, true); else TG_LAUNCH(8, 1, false); }
 #undef TG_LAUNCH
   return tb_launched("gcn layer kernel launch failed: ");
+}
+
+// The layer with a consumer of its output in the epilogue (the header has the contract): the dispatch of truss_gcn_layer over the
+// HEAD / POOL instantiations of the same two kernels.
+extern "C" int truss_gcn_layer_fused(const truss_gcn_layer_args_t *a, const truss_gcn_epilogue_t *e, void *stream) {
+  if (!a || !e) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer_fused: NULL argument");
+  if (int rc = tb_gcn_fused_check(a, e)) return rc;
+  if (a->w_bf16x3)
+    if (int rc = tb_gcn_bf16x3_check(a)) return rc;
+  if (a->n_batch == 0) return TRUSS_OK;
+  const bool head = e->kind == TRUSS_GCN_EPI_HEAD;
+  const int NW = a->n_nodes > 128 ? 8 : 4;
+  GcnFusedDev P;
+  (GcnLayerDev &)P = tg_layer_dev(a, 32 * NW);
+  P.w2 = e->w2; P.bias2 = e->bias2; P.adj2 = e->adj2; P.nbr2 = e->nbr2; P.out2 = e->out2; P.pool = e->pool;
+  P.a2_stride = e->a2_batch_stride;
+  P.out2_stride = e->out2_row_stride ? e->out2_row_stride : e->c2;
+  P.pool_stride = e->pool_row_stride ? e->pool_row_stride : a->c_out;
+  P.c2 = head ? e->c2 : 0; P.act2 = e->act2;
+  P.Kn2 = head ? (e->nbr2 ? e->k_nbr2 : a->n_nodes) : 0;
+  const int CB = a->c_out <= 32 ? 1 : 7;
+  const size_t lds_epi = tg_epi_lds_bytes(NW);
+  const unsigned grid = (unsigned)((a->n_batch + P.GB - 1) / P.GB);
+  hipStream_t st = (hipStream_t)stream;
+  if (a->w_bf16x3) {
+    const int KP = (a->k_in + 15) & ~15;
+    const size_t MTb = 32 * (size_t)NW;
+    size_t lds3 = MTb * TG_LD * 4 + 2 * 3 * MTb * 32 + 2 * 3 * 224 * 32;     // the slab loop's footprint, as truss_gcn_layer asks for it
+    if (lds3 < lds_epi) lds3 = lds_epi;
+#define TG_LAUNCH3E(nw, kt, epi)                                                                                                  \
+  do {                                                                                                                            \
+    static TbLdsOptIn optin;                                                                                                      \
+    if (int rc = optin.ensure((const void *)truss_gcn_layer_bf3_kernel<nw, kt, epi>)) return rc;                                  \
+    hipLaunchKernelGGL((truss_gcn_layer_bf3_kernel<nw, kt, epi>), dim3(grid), dim3(64 * nw), lds3, st, P, a->w_bf16x3, KP);       \
+  } while (0)
+#define TG_LAUNCH3(nw, kt) do { if (head) TG_LAUNCH3E(nw, kt, TG_EPI_HEAD); else TG_LAUNCH3E(nw, kt, TG_EPI_POOL); } while (0)
+    if (NW == 4) { if (P.Kn <= 6) TG_LAUNCH3(4, 6); else TG_LAUNCH3(4, 9); }
+    else { if (P.Kn <= 6) TG_LAUNCH3(8, 6); else TG_LAUNCH3(8, 9); }
+#undef TG_LAUNCH3
+#undef TG_LAUNCH3E
+    return tb_launched("gcn fused layer (bf16x3) kernel launch failed: ");
+  }
+  size_t lds = tg_lds_bytes(NW, CB, a->n_nodes, P.Kn);
+  if (lds < lds_epi) lds = lds_epi;
+  if (lds > 160 * 1024) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer_fused: tile does not fit the LDS");
+#define TG_LAUNCHE(nw, cb, vec, epi)                                                                             \
+  do {                                                                                                           \
+    static TbLdsOptIn optin;                                                                                     \
+    if (int rc = optin.ensure((const void *)truss_gcn_layer_kernel<nw, cb, vec, epi>)) return rc;                \
+    hipLaunchKernelGGL((truss_gcn_layer_kernel<nw, cb, vec, epi>), dim3(grid), dim3(64 * nw), lds, st, P);       \
+  } while (0)
+#define TG_LAUNCH(nw, cb, vec) do { if (head) TG_LAUNCHE(nw, cb, vec, TG_EPI_HEAD); else TG_LAUNCHE(nw, cb, vec, TG_EPI_POOL); } while (0)
+  const bool vec = P.x_vec && P.w_vec;
+  if (NW == 4 && CB == 7) { if (vec) TG_LAUNCH(4, 7, true); else TG_LAUNCH(4, 7, false); }
+  else if (NW == 4) { if (vec) TG_LAUNCH(4, 1, true); else TG_LAUNCH(4, 1, false); }
+  else if (CB == 7) { if (vec) TG_LAUNCH(8, 7, true); else TG_LAUNCH(8, 7, false); }
+  else { if (vec) TG_LAUNCH(8, 1, true); else TG_LAUNCH(8, 1, false); }
+#undef TG_LAUNCH
+#undef TG_LAUNCHE
+  return tb_launched("gcn fused layer kernel launch failed: ");
 }
 
 #ifdef TRUSS_GCN_STAMPS

@@ -38,7 +38,8 @@
   X(replay_scatter, truss_replay_scatter, false)                 \
   X(replay_gather, truss_replay_gather, false)                   \
   X(reward, truss_reward, false)                                 \
-  X(archive_merge, truss_archive_merge, false)
+  X(archive_merge, truss_archive_merge, false)                   \
+  X(gcn_layer_fused, truss_gcn_layer_fused, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -293,6 +294,49 @@ void gcn_layer(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tenso
   a.accumulate = accumulate ? 1 : 0;
   a.w_bf16x3 = (const uint16_t *)ptr<const int16_t>(b, w_split, at::kShort, "w_split", 3 * 224 * ((a.k_in + 15) / 16 * 16));
   check_rc(b, b.gcn_layer(&a, (void *)stream), "truss_gcn_layer");
+}
+
+// the same layer with a consumer of its output V in the epilogue of the launch: kind 1 (head) out2 = act2(adj2 @ (V @ w2^T) + bias2),
+// kind 2 (pool) pool = V.sum(dim=1); out (V itself) is optional == truss_gcn_layer_fused
+void gcn_layer_fused(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
+                     const OT &out, int64_t act, const OT &w_split, int64_t kind, const OT &w2, const OT &bias2, const OT &adj2, const OT &nbr2,
+                     int64_t act2, const OT &out2, const OT &pool) {
+  const Backend &b = backend(lib);
+  need(b.gcn_layer_fused, "truss_gcn_layer_fused");
+  TORCH_CHECK(x.dim() == 3 && w.dim() == 2 && w.size(1) == x.size(2), "truss_mi355: gcn_layer_fused: x [B, N, K], w [C, K]");
+  const int64_t B = x.size(0), N = x.size(1), K = x.size(2), C = w.size(0);
+  truss_gcn_layer_args_t a = layer_args(b, B, N, K, C, act, &x, adj, nbr, w);
+  a.bias = ptr<const float>(b, bias, at::kFloat, "bias", C);
+  TORCH_CHECK(!present(out) || (out->dim() == 3 && out->size(0) == B && out->size(1) == N && out->size(2) == C),
+              "truss_mi355: gcn_layer_fused: out must be [B, N, C]");
+  a.out = ptr<float>(b, out, at::kFloat, "out");
+  a.w_bf16x3 = (const uint16_t *)ptr<const int16_t>(b, w_split, at::kShort, "w_split", 3 * 224 * ((K + 15) / 16 * 16));
+  truss_gcn_epilogue_t e{};
+  e.struct_size = sizeof e;
+  e.kind = (int32_t)kind;
+  e.act2 = (int32_t)act2;
+  if (present(w2)) {
+    TORCH_CHECK(w2->dim() == 2 && w2->size(1) == C, "truss_mi355: gcn_layer_fused: w2 must be [c2, C]");
+    e.w2 = ptr<const float>(b, *w2, at::kFloat, "w2");
+    e.c2 = (int32_t)w2->size(0);
+  }
+  e.bias2 = ptr<const float>(b, bias2, at::kFloat, "bias2", e.c2);
+  if (present(adj2)) {
+    check_adj(*adj2, B, N);
+    e.adj2 = ptr<const float>(b, *adj2, at::kFloat, "adj2");
+    e.a2_batch_stride = adj2->dim() == 3 ? N * N : 0;
+  }
+  if (present(nbr2)) {
+    TORCH_CHECK(nbr2->dim() == 2 && nbr2->size(0) == N, "truss_mi355: nbr2 must be [N, K]");
+    e.nbr2 = ptr<const int16_t>(b, *nbr2, at::kShort, "nbr2");
+    e.k_nbr2 = (int32_t)nbr2->size(1);
+  }
+  TORCH_CHECK(!present(out2) || (out2->dim() == 3 && out2->size(0) == B && out2->size(1) == N && out2->size(2) == e.c2),
+              "truss_mi355: gcn_layer_fused: out2 must be [B, N, c2]");
+  e.out2 = ptr<float>(b, out2, at::kFloat, "out2");
+  TORCH_CHECK(!present(pool) || (pool->dim() == 2 && pool->size(0) == B && pool->size(1) == C), "truss_mi355: gcn_layer_fused: pool must be [B, C]");
+  e.pool = ptr<float>(b, pool, at::kFloat, "pool");
+  check_rc(b, b.gcn_layer_fused(&a, &e, (void *)stream), "truss_gcn_layer_fused");
 }
 
 // a whole level of GCN layers in one launch: out[i] = act[i](adj[i] @ (x[i] @ w[i]^T) + bias[i]); x_agg (empty, or one tensor per
@@ -620,6 +664,8 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("archive_merge(int lib, int stream, int max_front, int n_slots, Tensor pts_in, Tensor n_in, Tensor y_in, Tensor sec_in, Tensor? slot_row, "
         "Tensor cand_points, Tensor cand_y, Tensor cand_sec, Tensor(a!) pts_out, Tensor(b!) y_out, Tensor(c!) sec_out, Tensor(d!) n_out, "
         "Tensor(e!)? accepted, Tensor(f!)? front_idx, Tensor(g!)? hv_front, Tensor(h!)? metrics) -> ()");
+  m.def("gcn_layer_fused(int lib, int stream, Tensor x, Tensor adj, Tensor? nbr, Tensor w, Tensor? bias, Tensor(a!)? out, int act, Tensor? w_split, "
+        "int kind, Tensor? w2, Tensor? bias2, Tensor? adj2, Tensor? nbr2, int act2, Tensor(b!)? out2, Tensor(c!)? pool) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

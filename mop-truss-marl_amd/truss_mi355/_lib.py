@@ -117,6 +117,7 @@ _ENTRIES = [
 # revised, move these lines into _ENTRIES as (symbol, argtypes, True) and delete this list.
 _LATER_ENTRIES = [
     ("truss_archive_merge", [C.POINTER(ArchiveArgs), _vp]),
+    ("truss_gcn_layer_fused", [_vp, _vp, _vp]),
 ]
 
 
@@ -150,6 +151,7 @@ class TrussLib:
         self.has_replay_ops = {"truss_replay_scatter", "truss_replay_gather"} <= found      # the replay buffer's fused append / sample
         self.has_reward = "truss_reward" in found
         self.has_archive = "truss_archive_merge" in found                                    # the fused archive update
+        self.has_gcn_fused = "truss_gcn_layer_fused" in found                                # a GCN layer with its consumer in the epilogue
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")
         self.backend = d.truss_backend().decode()

@@ -218,6 +218,43 @@ def gcn_layer(lib, x, adj, w, bias, act, nbr=None, out=None, accumulate=False, p
     return out
 
 
+def _gcn_layer_fused(lib, x, adj, w, bias, act, nbr, precision, w_split, out, kind, w2=None, bias2=None, adj2=None, nbr2=None, act2=None,
+                     out2=None, pool=None):
+    """`truss_gcn_layer_fused`: the layer of `gcn_layer` with a consumer of its output in the epilogue of the same launch"""
+    from . import ops
+    B, N, K = x.shape
+    C = w.shape[0]
+    flat = lambda a: a[0] if a.dim() == 3 and a.shape[0] == 1 else a
+    adj = flat(adj.contiguous())
+    code = {None: 0, "relu": 1, "sigmoid": 2}
+    ws = None
+    if precision == "bf16x3" and C > 32 and K % 4 == 0 and x.data_ptr() % 16 == 0 and (nbr.shape[1] if nbr is not None else N) <= 9:
+        ws = w_split if w_split is not None else split_weights(lib, w)
+    if adj2 is not None:
+        adj2 = flat(adj2.contiguous())
+    ops.call(ops.namespace().gcn_layer_fused, ops.bind(lib), ops.stream_of(x.device), x, adj, nbr, w, bias, out, code[act], ws, kind,
+             w2, bias2, adj2, nbr2, code[act2], out2, pool)
+
+
+def gcn_layer_head(lib, x, adj, w, bias, act, w2, bias2, adj2, act2, nbr=None, nbr2=None, precision="bf16x3", w_split=None, out=None):
+    """A hidden GCN layer and the narrow layer that consumes it in ONE launch (`truss_gcn_layer_fused`, head epilogue):
+    act2(adj2 @ (V @ w2.T) + bias2) [B, N, c2] with V = act(adj @ (x @ w.T) + bias) as `gcn_layer` computes it -- V goes from the
+    accumulators through LDS into the head and is written to HBM only if `out` [B, N, C] is given.  w2 [c2 <= 8, C] =
+    nn.Linear.weight of the head; adj2 / nbr2: the head's own adjacency and pattern (as adj / nbr); the rest as for `gcn_layer`."""
+    out2 = torch.empty((x.shape[0], x.shape[1], w2.shape[0]), dtype=torch.float32, device=x.device)
+    _gcn_layer_fused(lib, x, adj, w, bias, act, nbr, precision, w_split, out, 1, w2, bias2, adj2, nbr2, act2, out2=out2)
+    return out2
+
+
+def gcn_layer_pool(lib, x, adj, w, bias, act, nbr=None, precision="bf16x3", w_split=None, out=None):
+    """A GCN layer and the sum of its output over the nodes of every graph in ONE launch (`truss_gcn_layer_fused`, pool epilogue):
+    act(adj @ (x @ w.T) + bias).sum(dim=1) [B, C], every one of the N rows counted; the layer's output itself is written to HBM
+    only if `out` [B, N, C] is given.  Arguments as for `gcn_layer`."""
+    pool = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
+    _gcn_layer_fused(lib, x, adj, w, bias, act, nbr, precision, w_split, out, 2, pool=pool)
+    return pool
+
+
 def level_forward(lib):
     """The fused forward of a whole level of GCN layers (`truss_gcn_level`, csrc/truss_gcn_level.h: one launch for every layer of
     every group) in the shape truss2D_RL._GcnLevel asks for: callable(groups, xs, ws, bs, want_grad) -> ([out_g [n, B, N, C]],
@@ -330,20 +367,27 @@ def path_graph_table(n_nodes):
     return t
 
 
-def actor_infer(lib, actor, ins, nbr=None, nbr_p=None):
+def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False):
     """truss2D_RL.multimodes_actor.forward (truss2D_RL.py:49-120) for inference, every GCN layer ONE launch of the fused MFMA
     kernel (`gcn_layer`: neighbourhood sum on the input rows, product with W^T on the matrix cores, bias + activation in the
     epilogue; H = X W never exists in HBM); the five second-level layers accumulate their sum x3 in place.  Same values as the
     module up to float32 summation order ((A X) W instead of A (X W)).
     nbr: the truss's neighbour table on the device (TrussTopology.neighbor_table()) for the layers over the node graph; nbr_p: the
     same for the Pareto graph (path_graph_table(P) when A_p comes from `pareto_graph`; None = dense, at most 64 members).  Shapes outside the kernel's envelope (a node graph without pattern above 64 nodes)
-    fall back to library GEMM + `gcn_aggregate`."""
+    fall back to library GEMM + `gcn_aggregate`.
+    fused: the three activations that inference writes only to read them back once stay on chip (`truss_gcn_layer_fused`, 11 launches
+    instead of 13): gcn_l1_4 is summed over the Pareto graph in its own epilogue (`gcn_layer_pool`), and the action heads gcn_l4_1 /
+    gcn_l4_2 run in the epilogues of gcn_l3_1 / gcn_l3_2 (`gcn_layer_head`; they read lin.weight as it is).  Same values up to float32
+    summation order; a layer outside the kernel's envelope takes the unfused path."""
     x_n, A_n, A_s, A_ts, A_cs, x_p, A_p = ins
 
-    def g(layer, x, a, act="relu", out=None, accumulate=False):
-        if isinstance(layer.lin.weight, torch.nn.parameter.UninitializedParameter):   # lazy layers: let the module materialise itself once
+    def materialise(layer, x, a):                           # lazy layers: let the module materialise itself once
+        if isinstance(layer.lin.weight, torch.nn.parameter.UninitializedParameter):
             with torch.no_grad():
                 layer(x[:1], a[:1] if a.dim() == 3 else a)
+
+    def g(layer, x, a, act="relu", out=None, accumulate=False):
+        materialise(layer, x, a)
         w, bvec = layer.lin.weight, layer.bias
         pat = nbr_p if a is A_p else nbr
         x = x.contiguous()
@@ -355,6 +399,28 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None):
             return h
         return out.add_(h) if accumulate else out.copy_(h)
 
+    def g_pool(layer, x, a):                                # g(layer, x, a).sum(dim=1) without the [B, P, H] tensor
+        materialise(layer, x, a)
+        pat = nbr_p if a is A_p else nbr
+        x = x.contiguous()
+        if not (fused and gcn_layer_supported(x.shape[1], layer.lin.weight.shape[0], pat)):
+            return g(layer, x, a).sum(dim=1)
+        wd, ws = layer_split_weights(lib, layer, x.shape[2])
+        return gcn_layer_pool(lib, x, a, wd, layer.bias.detach(), "relu", pat, w_split=ws)
+
+    def g_head(layer, head, x, a, a2):                      # g(head, g(layer, x, a), a2, "sigmoid") without the hidden tensor
+        materialise(layer, x, a)
+        if isinstance(head.lin.weight, torch.nn.parameter.UninitializedParameter):
+            materialise(head, x.new_zeros((1, x.shape[1], layer.lin.weight.shape[0])), a2)
+        pat, pat2 = nbr_p if a is A_p else nbr, nbr_p if a2 is A_p else nbr
+        x = x.contiguous()
+        w2 = head.lin.weight
+        if not (w2.shape[0] <= 8 and gcn_layer_supported(x.shape[1], layer.lin.weight.shape[0], pat)
+                and gcn_layer_supported(x.shape[1], w2.shape[0], pat2)):
+            return g(head, g(layer, x, a), a2, "sigmoid")
+        wd, ws = layer_split_weights(lib, layer, x.shape[2])
+        return gcn_layer_head(lib, x, a, wd, layer.bias.detach(), "relu", w2.detach(), head.bias.detach(), a2, "sigmoid", pat, pat2, w_split=ws)
+
     a = actor
     if x_n.shape[2] % 4 and gcn_layer_supported(x_n.shape[1], 200, nbr):
         # 13 node features -> 16 (zero columns, matched by zero columns of the three input kernels): 16-byte loads, bf16x3 product
@@ -364,7 +430,7 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None):
                     layer(x_n[:1], A_n[:1] if A_n.dim() == 3 else A_n)
         x_n = torch.nn.functional.pad(x_n, (0, 4 - x_n.shape[2] % 4))
     x11, x12, x13 = g(a.gcn_l1_1, x_n, A_n), g(a.gcn_l1_2, x_n, A_n), g(a.gcn_l1_3, x_n, A_n)
-    x14 = g(a.gcn_l1_4, x_p, A_p).sum(dim=1)                                             # GlobalSumPool over the Pareto graph
+    x14 = g_pool(a.gcn_l1_4, x_p, A_p)                                                   # GlobalSumPool over the Pareto graph
     B, H = x14.shape
     x14 = x14.unsqueeze(-1).expand(B, H, x11.shape[1]).reshape(B, x11.shape[1], H)      # _tile_pool (:87-93)
     x3 = g(a.gcn_l2_1, x11, A_n)
@@ -372,8 +438,11 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None):
     g(a.gcn_l2_3, x12, A_cs, out=x3, accumulate=True)
     g(a.gcn_l2_4, x13, A_s, out=x3, accumulate=True)
     g(a.gcn_l2_5, x14.contiguous(), A_n, out=x3, accumulate=True)
-    x31, x32 = g(a.gcn_l3_1, x3, A_n), g(a.gcn_l3_2, x3, A_s)
-    return g(a.gcn_l4_1, x31, A_n, "sigmoid"), g(a.gcn_l4_2, x32, A_n, "sigmoid")
+    if not fused:
+        x31, x32 = g(a.gcn_l3_1, x3, A_n), g(a.gcn_l3_2, x3, A_s)
+        return g(a.gcn_l4_1, x31, A_n, "sigmoid"), g(a.gcn_l4_2, x32, A_n, "sigmoid")
+    materialise(a.gcn_l3_1, x3, A_n), materialise(a.gcn_l3_2, x3, A_s)                  # (lazy layers: in the order of the unfused path)
+    return g_head(a.gcn_l3_1, a.gcn_l4_1, x3, A_n, A_n), g_head(a.gcn_l3_2, a.gcn_l4_2, x3, A_s, A_n)
 
 
 class DeviceReplay:
@@ -571,8 +640,11 @@ class BatchedMARL:
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
                  pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None,
                  level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None,
-                 archive_path: str | None = None):
-        """archive_path: how a game step updates the archives -- "torch" (candidate buffers, one `truss_front` launch and gathers by
+                 archive_path: str | None = None, actor_path: str | None = None):
+        """actor_path: how the rollout evaluates an actor -- "layers" (13 launches of the fused layer kernel, the default) or "fused"
+        (`actor_infer(fused=True)`: the Pareto pool and the two action heads run in the epilogues of the layers that feed them, 11
+        launches; needs a library with `truss_gcn_layer_fused`); None: "fused" if the environment has TRUSS_ACTOR=fused, else "layers".
+        archive_path: how a game step updates the archives -- "torch" (candidate buffers, one `truss_front` launch and gathers by
         framework operators, the default) or "hip" (one `truss_archive_merge` launch per chunk, per step in the design game; needs a
         library with that entry; the archive then lives in two sets of buffers that swap roles); None: "hip" if the environment has
         TRUSS_ARCHIVE=hip, else "torch".  Both play the same game, bit for bit.
@@ -644,7 +716,14 @@ class BatchedMARL:
                 raise ValueError(f"archive_path='hip': max_front {self.P} + {3 * self.Gm} candidate slots exceed the "
                                  f"{_lib.ARCHIVE_MAXROWS} rows of truss_archive_merge")
         self.archive_path = archive_path
-        self._arch_spare = None        # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
+        if actor_path is None:
+            actor_path = "fused" if os.environ.get("TRUSS_ACTOR", "layers") == "fused" else "layers"
+        if actor_path not in ("layers", "fused"):
+            raise ValueError(f"actor_path must be 'layers' or 'fused', got {actor_path!r}")
+        if actor_path == "fused" and not self.lib.has_gcn_fused:
+            raise ValueError(f"actor_path='fused': {self.lib.path} has no truss_gcn_layer_fused")
+        self.actor_path = actor_path
+        self._arch_spare = None       # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
         if self.device.type == "cuda":
             import truss2D_RL
             truss2D_RL.set_level_backward(_level_backward_hook(self.lib) if level_backward == "hip" else None, "cuda")
@@ -750,7 +829,8 @@ class BatchedMARL:
         with torch.no_grad():
             for ag in self.rl.agents:
                 g, t = actor_infer(self.lib, ag.actor_model, [actor_in[0], self.A_n[0], actor_in[2], actor_in[3], actor_in[4],
-                                                              actor_in[5], actor_in[6]], nbr=self.nbr, nbr_p=self.nbr_p)
+                                                              actor_in[5], actor_in[6]], nbr=self.nbr, nbr_p=self.nbr_p,
+                                     fused=self.actor_path == "fused")
                 if explore:                                           # truss2D_RL.OUNoise.gen_noise per scalar (:41-48), all columns at once
                     for out, noises in ((g, ag.noise_geo), (t, ag.noise_topo)):
                         th_dt, mu, sg = self._noise_vectors(noises)
@@ -791,8 +871,8 @@ class BatchedMARL:
                 with torch.no_grad():
                     for ag_ in self.rl.agents:
                         actor_infer(self.lib, ag_.actor_model, [S[0][:1], self.A_n[0], S[2][:1], S[3][:1], S[4][:1], S[6][:1], S[7][:1]],
-                                    nbr=self.nbr, nbr_p=self.nbr_p)
-                snap = [[p.detach().clone() for p in n.parameters()] for n in nets]
+                                    nbr=self.nbr, nbr_p=self.nbr_p, fused=self.actor_path == "fused")
+                snap =[[p.detach().clone() for p in n.parameters()] for n in nets]
                 osnap = [t.clone() for t in self.rl.critics_opt.state_tensors()]    # [] = no step taken yet (one optimiser for the three critics)
                 n_loss = [len(ag_.c_loss) for ag_ in self.rl.agents]
                 side = torch.cuda.Stream(device=self.device)

@@ -1,0 +1,162 @@
+"""Diagnostic: actor inference as 13 launches of the fused layer kernel (marl.actor_infer) against the path that keeps the Pareto pool
+and the two action heads in the epilogues of the layers that feed them (actor_infer(fused=True): 11 launches, truss_gcn_layer_fused),
+timed in ONE process.
+
+    python tools/actor_probe.py [OUT_DIR]        -> OUT_DIR/actor_probe.json   (default OUT_DIR: build/actor_probe)
+
+The driver starts two child processes, one after the other, each once and under its own `timeout` (no retry; the second only if the
+first ended well).  "time" reports the median wall time (host side included) of 60 synchronised actor_infer calls after 10 warm-up
+calls per path, in alternating blocks of 15: layers, fused, layers again, ... (the two layers medians give the spread a difference
+has to exceed), and the largest difference between the two paths' outputs.  "launches" counts the device kernels of one call of
+each path with torch.profiler (a run of its own: tracing slows the host) and lists, with their device time, the three fused launches
+next to the launches they replace (the 200 -> 200 layers that feed the heads, the heads, the Pareto layer and the reduction).
+Shapes: the reference's actor (hidden 200, heads 2 and 3) at the small_roof widths (16 nodes), 4096 and 14 336 (env, member) pairs
+with a Pareto graph of 20 members (the train game) and 4096 pairs with 50 members (the design game)."""
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "mop-truss-marl_amd"))
+
+SHAPES = (          # (label, pairs, P)
+    ("small_roof 4096 pairs, P 20", 4096, 20),
+    ("small_roof 14336 pairs, P 20", 14336, 20),
+    ("small_roof 4096 pairs, P 50", 4096, 50),
+)
+ROUNDS, BLOCK = 4, 15          # timed calls per path: ROUNDS alternating blocks of BLOCK
+
+
+def setup(B, P, dev):
+    import numpy as np
+    import torch
+    import truss_mi355 as tm
+    from truss_mi355 import marl
+    import truss2D_RL as RL
+    torch.manual_seed(B + P)
+    topo = tm.TrussTopology.grid(8)
+    N, tab = topo.N, topo.neighbor_table()
+    patt = np.zeros((N, N), bool)
+    for i in range(N):
+        patt[i, tab[i][tab[i] >= 0]] = True
+    patt = torch.tensor(patt, device=dev)
+    actor = RL.multimodes_actor(200, 2, 3).to(dev)
+    r = lambda *s: torch.rand(*s, device=dev)
+    pts = torch.rand(B, P, 4, dtype=torch.float64, device=dev)
+    x_p, A_p = marl.pareto_graph(pts, torch.randint(1, P + 1, (B,), device=dev), torch.zeros(B, dtype=torch.long, device=dev), P)
+    A_n = torch.tensor(topo.normalized_adjacency()[0], device=dev)
+    ins = [r(B, N, 13), A_n, r(B, N, N) * patt, r(B, N, N) * patt, r(B, N, N) * patt, x_p, A_p]
+    kw = dict(nbr=torch.tensor(tab, device=dev), nbr_p=torch.tensor(marl.path_graph_table(P), device=dev))
+    return actor, ins, kw
+
+
+def paths(lib, actor, ins, kw):
+    import torch
+    from truss_mi355 import marl
+
+    def run(fused):
+        with torch.no_grad():
+            return marl.actor_infer(lib, actor, ins, fused=fused, **kw)
+    return {"layers": lambda: run(False), "fused": lambda: run(True)}
+
+
+def child_time():
+    import torch
+    import truss_mi355 as tm
+    dev = torch.device("cuda")
+    lib = tm.load()
+    out = {}
+    for label, B, P in SHAPES:
+        actor, ins, kw = setup(B, P, dev)
+        fn = paths(lib, actor, ins, kw)
+
+        def times(f, n):
+            ts = []
+            for _ in range(n):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                f()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e6)
+            return ts
+
+        for f in fn.values():
+            times(f, 10)                                               # warm-up of every shape the timed calls use
+        ts = {"layers": [], "fused": [], "layers_again": []}
+        for _ in range(ROUNDS):                                        # alternating blocks: layers, fused, layers, ...
+            for k in ts:
+                ts[k] += times(fn["fused" if k == "fused" else "layers"], BLOCK)
+        res = {"call_us": {k: round(statistics.median(v), 1) for k, v in ts.items()}, "calls_per_median": ROUNDS * BLOCK}
+        a, b = fn["layers"](), fn["fused"]()
+        res["max_abs_difference"] = max(float((x - y).abs().max()) for x, y in zip(a, b))
+        out[label] = res
+        del actor, ins, kw, fn, a, b
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
+def child_launches():
+    import torch
+    from torch.profiler import profile, ProfilerActivity
+    import truss_mi355 as tm
+    dev = torch.device("cuda")
+    lib = tm.load()
+    out = {}
+    for label, B, P in SHAPES:
+        actor, ins, kw = setup(B, P, dev)
+        for path, f in paths(lib, actor, ins, kw).items():
+            for _ in range(3):
+                f()
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+                f()
+                torch.cuda.synchronize()
+            kern = {}
+            for e in prof.key_averages():
+                if e.device_type == torch.autograd.DeviceType.CUDA:
+                    us = getattr(e, "device_time_total", None)
+                    us = e.cuda_time_total if us is None else us
+                    c, t = kern.get(e.key, (0, 0.0))
+                    kern[e.key] = (c + e.count, t + us)
+            # the native launches one by one, in launch order: the fourth is gcn_l1_4 (the Pareto layer), the last four (layers) are
+            # gcn_l3_1, gcn_l3_2 and the two heads; fused: the last two are the head launches
+            dev_events = sorted((e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "truss_" in e.name),
+                                key=lambda e: e.time_range.start)
+            seq = [[e.name.replace("void ", "").split("(")[0], round(e.time_range.end - e.time_range.start, 1)] for e in dev_events]
+            out[f"{label} path={path}"] = {
+                "launches": sum(c for c, _ in kern.values()), "device_us": round(sum(t for _, t in kern.values()), 1),
+                "kernels": {k[:110]: {"count": c, "device_us": round(t, 1)} for k, (c, t) in sorted(kern.items())},
+                "native_in_launch_order": seq}
+        del actor, ins, kw
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
+def main():
+    out_dir = os.path.abspath(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "build", "actor_probe"))
+    os.makedirs(out_dir, exist_ok=True)
+    me = os.path.abspath(__file__)
+    env = dict(os.environ, TMPDIR="/tmp")
+    result = {}
+    for step, limit in (("time", "300"), ("launches", "180")):
+        p = subprocess.run(["timeout", "-k", "10", limit, sys.executable, me, "--child", step], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True)
+        with open(os.path.join(out_dir, step + ".err"), "w") as f:
+            f.write(p.stderr[-20000:])
+        if p.returncode != 0:
+            print(f"the {step} step failed with status {p.returncode}\n{p.stderr[-2000:]}", file=sys.stderr)
+            sys.exit(1)
+        result[step] = json.loads(p.stdout.strip().splitlines()[-1])
+        with open(os.path.join(out_dir, "actor_probe.json"), "w") as f:
+            json.dump(result, f, indent=1)
+    print(json.dumps(result, indent=1))
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[1] == "--child":
+        {"time": child_time, "launches": child_launches}[sys.argv[2]]()
+    else:
+        main()
