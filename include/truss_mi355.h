@@ -459,6 +459,22 @@ typedef struct truss_gcn_epilogue {
 } truss_gcn_epilogue_t;
 int truss_gcn_layer_fused(const truss_gcn_layer_args_t *layer, const truss_gcn_epilogue_t *epi, void *stream);
 
+/* The split-weight layer at REDUCED precision, for inference that does not need float32 products (rollout actions get exploration
+ * noise on top and are decoded to a 0.01 grid / +-1 sections).  `layer` and `epi` are exactly what truss_gcn_layer /
+ * truss_gcn_layer_fused take, with the same checks; epi == NULL is the plain layer.  layer->w_bf16x3 must be set (TRUSS_EINVAL
+ * otherwise: this entry is the split-weight path only, with its envelope), and the same [3][224][kp] image serves every value of
+ *   bf16_terms  3  "bf16x3": the six partial products x_i w_j, i + j <= 2 -- the very kernels the two entries above launch
+ *               2  "bf16x2": x1 w0 + x0 w1 + x0 w0, operands truncated to two bf16 terms (16 significant bits)
+ *               1  "bf16"  : x0 w0, operands truncated to one bf16 term (8 significant bits)
+ *               anything else: TRUSS_EINVAL.
+ * Accumulation stays float32; bias, activation, accumulation into out and the epilogues (the head's own product included) are
+ * float32 as before.  Operands are TRUNCATED, not rounded to nearest (that is what lets one weight image serve all three): every
+ * product is therefore biased towards zero, by up to 2^-6 of its size with one term and 2^-13 with two.  Against float64, with
+ * Mag = |A| (|X| |W|^T) + |b| (+ |out0|):  |out - ref| <= (tau + 1e-6) Mag,  tau = 2^-13 (two terms), 2^-6 (one term).
+ * n_batch == 0: TRUSS_OK, no launch.  Launches nothing and writes nothing on any refusal; neither allocates nor synchronises;
+ * capturable; bitwise reproducible.  Optional entry of ABI version 3 (a library may lack it). */
+int truss_gcn_layer_terms(const truss_gcn_layer_args_t *layer, const truss_gcn_epilogue_t *epi, int32_t bf16_terms, void *stream);
+
 /* A whole LEVEL of GCN layers in one launch: layers[i] as for truss_gcn_layer, for n_layers layers that do not depend on each other
  * -- the layers of one depth of the reference's actor / critic graphs (truss2D_RL.py:86-103, 116-133), of one network or of
  * several.  replaces: the forward passes of the MADDPG update (truss2D_RL.py:561-629: 19 network passes of 13 / 21 GCN layers at

@@ -615,6 +615,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
 // 32-byte rows, the two 16-byte halves of a row swapped in every other group of 8 rows (conflict-free ds_read_b128 without padding).
 // Envelope: the hidden layers (c_out 33..224, k_in % 4 == 0, x 16-byte aligned, <= 9 terms per row); everything else takes the
 // float32 kernel.
+//
+// Fewer terms (truss_gcn_layer_terms; template parameter T, the number of bf16 terms per operand: 3, 2 or 1).  The kept partial
+// products are those x_i w_j with i + j <= T - 1 -- T = 3: the six above; T = 2 ("bf16x2"): x1 w0 + x0 w1 + x0 w0; T = 1 ("bf16"):
+// x0 w0 -- small ones first.  Both operands stay TRUNCATED to their first T terms: X' by tg_split_term, W by reading planes t < T
+// of the same [3][224][kp] image, so one weight image serves all three precisions and gcn_reference.split3 is the host model of
+// all of them.  What is left out of a product a w is below tau_T |a| |w|: tau_2 = 2^-13 (a1 w1 < 2^-14, two remainders < 2^-15
+// each), tau_1 = 2^-6.  Truncation rounds every operand towards zero, so "bf16" biases every PRODUCT towards zero (a product of
+// two truncated operands is never larger in magnitude than the exact one); with T = 2 the same bias is 2^-13 of a product.  Per
+// wave and 16-k slab: 42 / 21 / 7 MFMAs and 41 / 32 / 23 sixteen-byte LDS operations.  Everything that is sized by the number
+// of terms -- the LDS images, the LDS-DMA count WI, the per-wave count WD and the vmcnt(WD) that goes with it -- is sized by T.
 typedef __bf16 tg_bf8 __attribute__((ext_vector_type(8)));
 typedef uint32_t tg_u4 __attribute__((ext_vector_type(4)));
 
@@ -656,14 +666,15 @@ typedef __attribute__((address_space(1))) const void tg_glob_void;
 
 // KT: neighbourhood terms per row that are gathered (6: the grid trusses -- a node joins at most five others; 9: any pattern the
 // register path takes).  Terms past k_nbr have coefficient 0, but every one of them is two 16-byte LDS reads per slab and thread.
-template <int NW, int KT, int EPI = TG_EPI_NONE>
+template <int NW, int KT, int EPI = TG_EPI_NONE, int T = 3>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void truss_gcn_layer_bf3_kernel(const typename TgArgs<EPI>::type P, const uint16_t *__restrict__ ws, int KP) {
   constexpr int MT = 32 * NW, NT = 64 * NW, CB = 7, WROWS = 32 * CB;
   static_assert(WROWS == TG_CP, "split-weight image rows");
+  static_assert(T >= 1 && T <= 3, "bf16 terms per operand");
   extern __shared__ __attribute__((aligned(16))) char tg_smem[];
   float *sXraw = (float *)tg_smem;                                   // [MT][TG_LD] float32 raw input rows of a slab
-  char *sXs = tg_smem + MT * TG_LD * 4;                              // [2][3][MT][32 B]    split aggregated rows (MFMA A operand)
-  char *sWs = sXs + 2 * 3 * MT * 32;                                 // [2][3][WROWS][32 B] split W slab, [col][k]
+  char *sXs = tg_smem + MT * TG_LD * 4;                              // [2][T][MT][32 B]    split aggregated rows (MFMA A operand)
+  char *sWs = sXs + 2 * T * MT * 32;                                 // [2][T][WROWS][32 B] split W slab, [col][k]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int N = P.N, Kn = P.Kn, K = P.K, C = P.C;
   const int g0 = blockIdx.x * P.GB;
@@ -694,14 +705,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
     }
   }
 
-  // staging.  X slab: two 16-byte chunks per thread through registers, as in the float32 kernel.  W slab (3 terms x 224 cols x two
-  // 16-byte halves = 21 wave-instructions of 1 KB): LDS-DMA (global_load_lds_dwordx4) -- lane i of instruction j fetches the chunk
+  // staging.  X slab: two 16-byte chunks per thread through registers, as in the float32 kernel.  W slab (T terms x 224 cols x two
+  // 16-byte halves = 7 T wave-instructions of 1 KB, 21 for T = 3): LDS-DMA (global_load_lds_dwordx4) -- lane i of instruction j fetches the chunk
   // that belongs at LDS position 64 j + i of the (swizzled) image, no registers, no ds_write.  Every wave issues exactly WD of
   // them (instruction numbers past the last repeat it), so that "at most WD vector-memory operations outstanding" means "everything
   // older than the last W slab has landed".
   constexpr int XC = MT * 4 / NT;                                    // = 2
-  constexpr int WI = 3 * WROWS * 2 / 64;                             // = 21 wave-instructions per slab
-  constexpr int WD = (WI + NW - 1) / NW;                             // per wave: 6 (NW = 4) or 3 (NW = 8)
+  constexpr int WI = T * WROWS * 2 / 64;                             // = 7 T wave-instructions per slab: 21, 14, 7
+  constexpr int WD = (WI + NW - 1) / NW;                             // per wave, NW = 4 / 8: 6 / 3 (T = 3), 4 / 2 (T = 2), 2 / 1 (T = 1)
+  static_assert(WI == 7 * T && WI % T == 0 && WD * NW >= WI && (WD - 1) * NW < WI, "LDS-DMA instructions of a W slab");
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
   tg_f4 rx[XC];
   auto fetch = [&](int k0) {
@@ -727,10 +739,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
     for (int c = 0; c < WD; ++c) {
       int j = uwave + c * NW;
       j = j < WI ? j : WI - 1;
-      const int t = j / (WI / 3), rem = (j % (WI / 3)) * 64 + lane;  // term; position inside the term's [224][2] image
+      const int t = j / (WI / T), rem = (j % (WI / T)) * 64 + lane;  // term; position inside the term's [224][2] image
       const int col = rem >> 1, h = (rem & 1) ^ ((col >> 3) & 1);
       const uint16_t *src = ws + ((long)t * TG_CP + col) * KP + kc + h * 8;
-      __builtin_amdgcn_global_load_lds((tg_glob_void *)src, (tg_lds_void *)(sWs + (buf * 3 * WROWS * 2 + j * 64) * 16), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((tg_glob_void *)src, (tg_lds_void *)(sWs + (buf * T * WROWS * 2 + j * 64) * 16), 16, 0, 0);
     }
   };
   auto gather = [&](int t_lo, int t_hi, tg_f4 &a0, tg_f4 &a1) {
@@ -741,11 +753,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
       a1 += cf[tt] * *(const tg_f4 *)(src + 4);
     }
   };
-  auto put_split = [&](int buf, const tg_f4 a0, const tg_f4 a1) {    // this thread's eight k of row ar, three terms
+  auto put_split = [&](int buf, const tg_f4 a0, const tg_f4 a1) {    // this thread's eight k of row ar, the first T terms
     float r[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
-      *(tg_u4 *)(sXs + (((buf * 3 + t) * MT + ar) * 2 + (ah ^ ((ar >> 3) & 1))) * 16) = tg_split_term(r, t == 2);
+    for (int t = 0; t < T; ++t)
+      *(tg_u4 *)(sXs + (((buf * T + t) * MT + ar) * 2 + (ah ^ ((ar >> 3) & 1))) * 16) = tg_split_term(r, t == T - 1);
   };
 
   tg_f16 acc[CB];
@@ -757,13 +769,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
 
   // Order of the vector-memory operations of a wave (they complete in order): [W 0] [X 0] [W 1] [X 1] | loop s: [X s+2] [W s+2].
   // Waiting for the registers of X s+2 (stash_x, end of iteration s) therefore implies that W s+1 has landed; the explicit
-  // "vmcnt(WD)" in front of the top barrier says the same thing for the reader of this code.
+  // "vmcnt(WD)" in front of the top barrier says the same thing for the reader of this code.  Every wave issues exactly WD LDS-DMA
+  // instructions per W slab, whatever T is, and the immediate IS the constant WD: at most the youngest W slab is outstanding.
   const int nslab = (K + TG_KS - 1) / TG_KS;
   dma_w(0, 0);
   fetch(0);
   stash_x();
   dma_w(TG_KS, 1);
-  if constexpr (WD == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WD) : "memory");
   tg_lds_barrier();
   fetch(TG_KS);
   {
@@ -779,29 +792,65 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
 #endif
   for (int s = 0; s < nslab; ++s) {
     TG_T(ta);
-    if constexpr (WD == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WD) : "memory");
     tg_lds_barrier();                                                // X'[s], raw slab s + 1 and W slab s are in LDS
     TG_T(tb);
     const int buf = s & 1;
     fetch((s + 2) * TG_KS);
-    tg_bf8 xa[3];
+    tg_bf8 xa[T];
 #pragma unroll
-    for (int t = 0; t < 3; ++t) xa[t] = *(const tg_bf8 *)(sXs + (((buf * 3 + t) * MT + mrow) * 2 + (mh ^ ((mrow >> 3) & 1))) * 16);
+    for (int t = 0; t < T; ++t) xa[t] = *(const tg_bf8 *)(sXs + (((buf * T + t) * MT + mrow) * 2 + (mh ^ ((mrow >> 3) & 1))) * 16);
     tg_f4 a0 = {0.0f, 0.0f, 0.0f, 0.0f}, a1 = a0;
+    if constexpr (T == 3) {
 #pragma unroll
-    for (int cb = 0; cb < CB; ++cb) {
-      const int col = cb * 32 + mcol;
-      tg_bf8 wb[3];
+      for (int cb = 0; cb < CB; ++cb) {
+        const int col = cb * 32 + mcol;
+        tg_bf8 wb[3];
 #pragma unroll
-      for (int t = 0; t < 3; ++t) wb[t] = *(const tg_bf8 *)(sWs + (((buf * 3 + t) * WROWS + col) * 2 + (mh ^ ((col >> 3) & 1))) * 16);
-      if (cb * 2 < KT) gather(cb * 2, cb * 2 + 2 < KT ? cb * 2 + 2 : KT, a0, a1);   // two terms between the MFMAs of each of the first column blocks
-      // small partial products first
-      acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[2], wb[0], acc[cb], 0, 0, 0);
-      acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1], wb[1], acc[cb], 0, 0, 0);
-      acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[2], acc[cb], 0, 0, 0);
-      acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1], wb[0], acc[cb], 0, 0, 0);
-      acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[1], acc[cb], 0, 0, 0);
-      acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[0], acc[cb], 0, 0, 0);
+        for (int t = 0; t < 3; ++t) wb[t] = *(const tg_bf8 *)(sWs + (((buf * 3 + t) * WROWS + col) * 2 + (mh ^ ((col >> 3) & 1))) * 16);
+        if (cb * 2 < KT) gather(cb * 2, cb * 2 + 2 < KT ? cb * 2 + 2 : KT, a0, a1);   // two terms between the MFMAs of each of the first column blocks
+        // small partial products first
+        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[2], wb[0], acc[cb], 0, 0, 0);
+        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1], wb[1], acc[cb], 0, 0, 0);
+        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[2], acc[cb], 0, 0, 0);
+        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1], wb[0], acc[cb], 0, 0, 0);
+        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[1], acc[cb], 0, 0, 0);
+        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[0], acc[cb], 0, 0, 0);
+      }
+    } else {
+      // T < 3.  With fewer MFMAs to place between them the scheduler would issue the operand reads of all seven column blocks and
+      // every gather read at the top of the slab -- more live registers than the 256 of two waves per SIMD, i.e. spills.  So the
+      // column blocks go in four regions {0, 1} {2, 3} {4, 5} {6} with a scheduling barrier behind each: the B operands of the next
+      // region are requested before the MFMAs of the present one (in flight over them), nothing moves across a region's end.
+      tg_bf8 wb[CB][T];
+      auto load_wb = [&](int lo, int hi) {
+#pragma unroll
+        for (int cb = lo; cb < hi; ++cb) {
+          const int col = cb * 32 + mcol;
+#pragma unroll
+          for (int t = 0; t < T; ++t) wb[cb][t] = *(const tg_bf8 *)(sWs + (((buf * T + t) * WROWS + col) * 2 + (mh ^ ((col >> 3) & 1))) * 16);
+        }
+      };
+      load_wb(0, 2);
+#pragma unroll
+      for (int r = 0; r < (CB + 1) / 2; ++r) {
+        const int lo = 2 * r, hi = lo + 2 < CB ? lo + 2 : CB;
+        load_wb(hi, hi + 2 < CB ? hi + 2 : CB);
+#pragma unroll
+        for (int cb = lo; cb < hi; ++cb) {
+          if (cb * 2 < KT) gather(cb * 2, cb * 2 + 2 < KT ? cb * 2 + 2 : KT, a0, a1);
+          // the products x_i w_j with i + j <= T - 1, small partial products first
+          if constexpr (T == 2) {
+            acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1], wb[cb][0], acc[cb], 0, 0, 0);
+            acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[cb][1], acc[cb], 0, 0, 0);
+          }
+          acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[cb][0], acc[cb], 0, 0, 0);
+          // (nine terms, two products: the four gather terms of a region in flight together are three registers too many for the
+          // head epilogue's instantiation -- the two column blocks of a region keep their gathers apart)
+          if constexpr (T == 2 && KT > 6) __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
     put_split(buf ^ 1, a0, a1);                                      // behind the last operand read of this slab
     TG_T(tc);
@@ -884,6 +933,42 @@ static GcnLayerDev tg_layer_dev(const truss_gcn_layer_args_t *a, int tile_rows) 
   return P;
 }
 
+// the layer and its epilogue as the HEAD / POOL instantiations take them
+static GcnFusedDev tg_fused_dev(const truss_gcn_layer_args_t *a, const truss_gcn_epilogue_t *e, int tile_rows) {
+  const bool head = e->kind == TRUSS_GCN_EPI_HEAD;
+  GcnFusedDev P;
+  (GcnLayerDev &)P = tg_layer_dev(a, tile_rows);
+  P.w2 = e->w2; P.bias2 = e->bias2; P.adj2 = e->adj2; P.nbr2 = e->nbr2; P.out2 = e->out2; P.pool = e->pool;
+  P.a2_stride = e->a2_batch_stride;
+  P.out2_stride = e->out2_row_stride ? e->out2_row_stride : e->c2;
+  P.pool_stride = e->pool_row_stride ? e->pool_row_stride : a->c_out;
+  P.c2 = head ? e->c2 : 0; P.act2 = e->act2;
+  P.Kn2 = head ? (e->nbr2 ? e->k_nbr2 : a->n_nodes) : 0;
+  return P;
+}
+
+// The launch of truss_gcn_layer_bf3_kernel<NW, KT, EPI, T> for a checked layer (every entry that takes split weights ends here).
+// LDS: the slab loop's footprint shrinks with T (77 824 / 55 296 / 32 768 bytes at NW = 4); a fused epilogue reuses it and
+// needs tg_epi_lds_bytes(NW), which is the larger one only for T = 1 at NW = 8.
+template <int EPI, int T>
+static int tg_launch_bf3(const typename TgArgs<EPI>::type &P, int NW, const uint16_t *ws, int k_in, hipStream_t st) {
+  const int KP = (k_in + 15) & ~15;
+  const size_t MT = 32 * (size_t)NW;
+  size_t lds = MT * TG_LD * 4 + 2 * T * MT * 32 + 2 * T * 224 * 32;
+  if (EPI != TG_EPI_NONE && lds < tg_epi_lds_bytes(NW)) lds = tg_epi_lds_bytes(NW);
+  const unsigned grid = (unsigned)((P.B + P.GB - 1) / P.GB);
+#define TG_LAUNCH3(nw, kt)                                                                                                        \
+  do {                                                                                                                            \
+    static TbLdsOptIn optin;                                                                                                      \
+    if (int rc = optin.ensure((const void *)truss_gcn_layer_bf3_kernel<nw, kt, EPI, T>)) return rc;                               \
+    hipLaunchKernelGGL((truss_gcn_layer_bf3_kernel<nw, kt, EPI, T>), dim3(grid), dim3(64 * nw), lds, st, P, ws, KP);              \
+  } while (0)
+  if (NW == 4) { if (P.Kn <= 6) TG_LAUNCH3(4, 6); else TG_LAUNCH3(4, 9); }
+  else { if (P.Kn <= 6) TG_LAUNCH3(8, 6); else TG_LAUNCH3(8, 9); }
+#undef TG_LAUNCH3
+  return TRUSS_OK;
+}
+
 extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
   if (!a) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: NULL argument");
   if (int rc = tb_gcn_layer_check(a, "truss_gcn_layer", 256, 0, false)) return rc;
@@ -895,19 +980,7 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
   if (a->w_bf16x3) {
     // product on the bf16 matrix cores at float32 accuracy (see truss_gcn_layer_bf3_kernel)
     if (int rc = tb_gcn_bf16x3_check(a)) return rc;
-    const int KP = (a->k_in + 15) & ~15;
-    const size_t MTb = 32 * (size_t)NW;
-    const size_t lds3 = MTb * TG_LD * 4 + 2 * 3 * MTb * 32 + 2 * 3 * 224 * 32;
-    const unsigned grid3 = (unsigned)((a->n_batch + P.GB - 1) / P.GB);
-#define TG_LAUNCH3(nw, kt)                                                                                                  \
-  do {                                                                                                                      \
-    static TbLdsOptIn optin;                                                                                                \
-    if (int rc = optin.ensure((const void *)truss_gcn_layer_bf3_kernel<nw, kt>)) return rc;                                 \
-    hipLaunchKernelGGL((truss_gcn_layer_bf3_kernel<nw, kt>), dim3(grid3), dim3(64 * nw), lds3, st, P, a->w_bf16x3, KP);      \
-  } while (0)
-    if (NW == 4) { if (P.Kn <= 6) TG_LAUNCH3(4, 6); else TG_LAUNCH3(4, 9); }
-    else { if (P.Kn <= 6) TG_LAUNCH3(8, 6); else TG_LAUNCH3(8, 9); }
-#undef TG_LAUNCH3
+    if (int rc = tg_launch_bf3<TG_EPI_NONE, 3>(P, NW, a->w_bf16x3, a->k_in, st)) return rc;
     return tb_launched("gcn layer (bf16x3) kernel launch failed: ");
   }
   const size_t lds = tg_lds_bytes(NW, CB, a->n_nodes, P.Kn);
@@ -938,34 +1011,14 @@ extern "C" int truss_gcn_layer_fused(const truss_gcn_layer_args_t *a, const trus
   if (a->n_batch == 0) return TRUSS_OK;
   const bool head = e->kind == TRUSS_GCN_EPI_HEAD;
   const int NW = a->n_nodes > 128 ? 8 : 4;
-  GcnFusedDev P;
-  (GcnLayerDev &)P = tg_layer_dev(a, 32 * NW);
-  P.w2 = e->w2; P.bias2 = e->bias2; P.adj2 = e->adj2; P.nbr2 = e->nbr2; P.out2 = e->out2; P.pool = e->pool;
-  P.a2_stride = e->a2_batch_stride;
-  P.out2_stride = e->out2_row_stride ? e->out2_row_stride : e->c2;
-  P.pool_stride = e->pool_row_stride ? e->pool_row_stride : a->c_out;
-  P.c2 = head ? e->c2 : 0; P.act2 = e->act2;
-  P.Kn2 = head ? (e->nbr2 ? e->k_nbr2 : a->n_nodes) : 0;
+  const GcnFusedDev P = tg_fused_dev(a, e, 32 * NW);
   const int CB = a->c_out <= 32 ? 1 : 7;
   const size_t lds_epi = tg_epi_lds_bytes(NW);
   const unsigned grid = (unsigned)((a->n_batch + P.GB - 1) / P.GB);
   hipStream_t st = (hipStream_t)stream;
   if (a->w_bf16x3) {
-    const int KP = (a->k_in + 15) & ~15;
-    const size_t MTb = 32 * (size_t)NW;
-    size_t lds3 = MTb * TG_LD * 4 + 2 * 3 * MTb * 32 + 2 * 3 * 224 * 32;     // the slab loop's footprint, as truss_gcn_layer asks for it
-    if (lds3 < lds_epi) lds3 = lds_epi;
-#define TG_LAUNCH3E(nw, kt, epi)                                                                                                  \
-  do {                                                                                                                            \
-    static TbLdsOptIn optin;                                                                                                      \
-    if (int rc = optin.ensure((const void *)truss_gcn_layer_bf3_kernel<nw, kt, epi>)) return rc;                                  \
-    hipLaunchKernelGGL((truss_gcn_layer_bf3_kernel<nw, kt, epi>), dim3(grid), dim3(64 * nw), lds3, st, P, a->w_bf16x3, KP);       \
-  } while (0)
-#define TG_LAUNCH3(nw, kt) do { if (head) TG_LAUNCH3E(nw, kt, TG_EPI_HEAD); else TG_LAUNCH3E(nw, kt, TG_EPI_POOL); } while (0)
-    if (NW == 4) { if (P.Kn <= 6) TG_LAUNCH3(4, 6); else TG_LAUNCH3(4, 9); }
-    else { if (P.Kn <= 6) TG_LAUNCH3(8, 6); else TG_LAUNCH3(8, 9); }
-#undef TG_LAUNCH3
-#undef TG_LAUNCH3E
+    if (int rc = head ? tg_launch_bf3<TG_EPI_HEAD, 3>(P, NW, a->w_bf16x3, a->k_in, st) : tg_launch_bf3<TG_EPI_POOL, 3>(P, NW, a->w_bf16x3, a->k_in, st))
+      return rc;
     return tb_launched("gcn fused layer (bf16x3) kernel launch failed: ");
   }
   size_t lds = tg_lds_bytes(NW, CB, a->n_nodes, P.Kn);
@@ -986,6 +1039,33 @@ extern "C" int truss_gcn_layer_fused(const truss_gcn_layer_args_t *a, const trus
 #undef TG_LAUNCH
 #undef TG_LAUNCHE
   return tb_launched("gcn fused layer kernel launch failed: ");
+}
+
+// The split-weight layer, plain (e == NULL) or with an epilogue, on the first `terms` bf16 terms of both operands (the header has the
+// contract).  terms == 3 launches the instantiations of the two entries above.
+extern "C" int truss_gcn_layer_terms(const truss_gcn_layer_args_t *a, const truss_gcn_epilogue_t *e, int32_t terms, void *stream) {
+  if (!a) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer_terms: NULL argument");
+  if (terms < 1 || terms > 3) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer_terms: bf16_terms 1..3");
+  if (int rc = e ? tb_gcn_fused_check(a, e) : tb_gcn_layer_check(a, "truss_gcn_layer_terms", 256, 0, false)) return rc;
+  if (!a->w_bf16x3) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer_terms: w_bf16x3 is NULL (the split-weight path only)");
+  if (int rc = tb_gcn_bf16x3_check(a)) return rc;
+  if (a->n_batch == 0) return TRUSS_OK;
+  const int NW = a->n_nodes > 128 ? 8 : 4;
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+#define TG_TERMS(epi, P) (terms == 3 ? tg_launch_bf3<epi, 3>(P, NW, a->w_bf16x3, a->k_in, st)     \
+                          : terms == 2 ? tg_launch_bf3<epi, 2>(P, NW, a->w_bf16x3, a->k_in, st)   \
+                                       : tg_launch_bf3<epi, 1>(P, NW, a->w_bf16x3, a->k_in, st))
+  if (!e) {
+    const GcnLayerDev P = tg_layer_dev(a, 32 * NW);
+    rc = TG_TERMS(TG_EPI_NONE, P);
+  } else {
+    const GcnFusedDev P = tg_fused_dev(a, e, 32 * NW);
+    rc = e->kind == TRUSS_GCN_EPI_HEAD ? TG_TERMS(TG_EPI_HEAD, P) : TG_TERMS(TG_EPI_POOL, P);
+  }
+#undef TG_TERMS
+  if (rc) return rc;
+  return tb_launched("gcn layer (bf16 terms) kernel launch failed: ");
 }
 
 #ifdef TRUSS_GCN_STAMPS

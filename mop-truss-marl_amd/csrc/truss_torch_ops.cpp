@@ -39,7 +39,8 @@
   X(replay_gather, truss_replay_gather, false)                   \
   X(reward, truss_reward, false)                                 \
   X(archive_merge, truss_archive_merge, false)                   \
-  X(gcn_layer_fused, truss_gcn_layer_fused, false)
+  X(gcn_layer_fused, truss_gcn_layer_fused, false)               \
+  X(gcn_layer_terms, truss_gcn_layer_terms, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -298,20 +299,19 @@ void gcn_layer(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tenso
 
 // the same layer with a consumer of its output V in the epilogue of the launch: kind 1 (head) out2 = act2(adj2 @ (V @ w2^T) + bias2),
 // kind 2 (pool) pool = V.sum(dim=1); out (V itself) is optional == truss_gcn_layer_fused
-void gcn_layer_fused(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
-                     const OT &out, int64_t act, const OT &w_split, int64_t kind, const OT &w2, const OT &bias2, const OT &adj2, const OT &nbr2,
-                     int64_t act2, const OT &out2, const OT &pool) {
-  const Backend &b = backend(lib);
-  need(b.gcn_layer_fused, "truss_gcn_layer_fused");
+// (the argument blocks of the two operators that take an epilogue)
+void fused_args(const Backend &b, truss_gcn_layer_args_t &a, truss_gcn_epilogue_t &e, const at::Tensor &x, const at::Tensor &adj, const OT &nbr,
+                const at::Tensor &w, const OT &bias, const OT &out, int64_t act, const OT &w_split, int64_t kind, const OT &w2, const OT &bias2,
+                const OT &adj2, const OT &nbr2, int64_t act2, const OT &out2, const OT &pool) {
   TORCH_CHECK(x.dim() == 3 && w.dim() == 2 && w.size(1) == x.size(2), "truss_mi355: gcn_layer_fused: x [B, N, K], w [C, K]");
   const int64_t B = x.size(0), N = x.size(1), K = x.size(2), C = w.size(0);
-  truss_gcn_layer_args_t a = layer_args(b, B, N, K, C, act, &x, adj, nbr, w);
+  a = layer_args(b, B, N, K, C, act, &x, adj, nbr, w);
   a.bias = ptr<const float>(b, bias, at::kFloat, "bias", C);
   TORCH_CHECK(!present(out) || (out->dim() == 3 && out->size(0) == B && out->size(1) == N && out->size(2) == C),
               "truss_mi355: gcn_layer_fused: out must be [B, N, C]");
   a.out = ptr<float>(b, out, at::kFloat, "out");
   a.w_bf16x3 = (const uint16_t *)ptr<const int16_t>(b, w_split, at::kShort, "w_split", 3 * 224 * ((K + 15) / 16 * 16));
-  truss_gcn_epilogue_t e{};
+  e = truss_gcn_epilogue_t{};
   e.struct_size = sizeof e;
   e.kind = (int32_t)kind;
   e.act2 = (int32_t)act2;
@@ -336,7 +336,32 @@ void gcn_layer_fused(int64_t lib, int64_t stream, const at::Tensor &x, const at:
   e.out2 = ptr<float>(b, out2, at::kFloat, "out2");
   TORCH_CHECK(!present(pool) || (pool->dim() == 2 && pool->size(0) == B && pool->size(1) == C), "truss_mi355: gcn_layer_fused: pool must be [B, C]");
   e.pool = ptr<float>(b, pool, at::kFloat, "pool");
+}
+void gcn_layer_fused(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
+                     const OT &out, int64_t act, const OT &w_split, int64_t kind, const OT &w2, const OT &bias2, const OT &adj2, const OT &nbr2,
+                     int64_t act2, const OT &out2, const OT &pool) {
+  const Backend &b = backend(lib);
+  need(b.gcn_layer_fused, "truss_gcn_layer_fused");
+  truss_gcn_layer_args_t a;
+  truss_gcn_epilogue_t e;
+  fused_args(b, a, e, x, adj, nbr, w, bias, out, act, w_split, kind, w2, bias2, adj2, nbr2, act2, out2, pool);
   check_rc(b, b.gcn_layer_fused(&a, &e, (void *)stream), "truss_gcn_layer_fused");
+}
+
+// the split-weight layer on the first `terms` bf16 terms of both operands (3: bf16x3, 2: bf16x2, 1: bf16); kind 0: the plain layer
+// (out required, accumulate allowed), kind 1 / 2: with the epilogue of gcn_layer_fused == truss_gcn_layer_terms
+void gcn_layer_terms(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
+                     const OT &out, int64_t act, const OT &w_split, int64_t kind, const OT &w2, const OT &bias2, const OT &adj2, const OT &nbr2,
+                     int64_t act2, const OT &out2, const OT &pool, bool accumulate, int64_t terms) {
+  const Backend &b = backend(lib);
+  need(b.gcn_layer_terms, "truss_gcn_layer_terms");
+  truss_gcn_layer_args_t a;
+  truss_gcn_epilogue_t e;
+  fused_args(b, a, e, x, adj, nbr, w, bias, out, act, w_split, kind, w2, bias2, adj2, nbr2, act2, out2, pool);
+  TORCH_CHECK(kind != 0 || present(out), "truss_mi355: gcn_layer_terms: out must be [B, N, C] for a plain layer (kind 0)");
+  a.accumulate = accumulate ? 1 : 0;
+  TORCH_CHECK(terms >= INT32_MIN && terms <= INT32_MAX, "truss_mi355: gcn_layer_terms: terms out of range");
+  check_rc(b, b.gcn_layer_terms(&a, kind == 0 ? nullptr : &e, (int32_t)terms, (void *)stream), "truss_gcn_layer_terms");
 }
 
 // a whole level of GCN layers in one launch: out[i] = act[i](adj[i] @ (x[i] @ w[i]^T) + bias[i]); x_agg (empty, or one tensor per
@@ -666,6 +691,9 @@ TORCH_LIBRARY(truss_mi355, m) {
         "Tensor(e!)? accepted, Tensor(f!)? front_idx, Tensor(g!)? hv_front, Tensor(h!)? metrics) -> ()");
   m.def("gcn_layer_fused(int lib, int stream, Tensor x, Tensor adj, Tensor? nbr, Tensor w, Tensor? bias, Tensor(a!)? out, int act, Tensor? w_split, "
         "int kind, Tensor? w2, Tensor? bias2, Tensor? adj2, Tensor? nbr2, int act2, Tensor(b!)? out2, Tensor(c!)? pool) -> ()");
+  m.def("gcn_layer_terms(int lib, int stream, Tensor x, Tensor adj, Tensor? nbr, Tensor w, Tensor? bias, Tensor(a!)? out, int act, Tensor? w_split, "
+        "int kind, Tensor? w2, Tensor? bias2, Tensor? adj2, Tensor? nbr2, int act2, Tensor(b!)? out2, Tensor(c!)? pool, bool accumulate, "
+        "int terms) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

@@ -193,6 +193,22 @@ def refresh_actor_caches(lib, actor):
             _refresh_split(lib, layer, hit)
 
 
+PRECISIONS = ("f32", "bf16x3", "bf16x2", "bf16")
+_BF16_TERMS = {"bf16x3": 3, "bf16x2": 2, "bf16": 1}         # bf16 terms per operand of the split-weight product
+
+
+def _check_precision(precision, what="precision"):
+    if precision not in PRECISIONS:
+        raise ValueError(f"{what} must be one of {', '.join(repr(p) for p in PRECISIONS)}, got {precision!r}")
+    return precision
+
+
+def _bf16_envelope(x, w, nbr):
+    """the split-weight kernel takes this layer (tb_gcn_bf16x3_check); every other layer runs on the float32 matrix cores under
+    every precision"""
+    return w.shape[0] > 32 and x.shape[2] % 4 == 0 and x.data_ptr() % 16 == 0 and (nbr.shape[1] if nbr is not None else x.shape[1]) <= 9
+
+
 def gcn_layer(lib, x, adj, w, bias, act, nbr=None, out=None, accumulate=False, precision="bf16x3", w_split=None):
     """One whole GCN layer through the hand-written MFMA kernel (`truss_gcn_layer`, csrc/truss_gcn.h):
     out = act(adj @ (x @ w.T) + bias), or out += ... with `accumulate`; float32 in and out, inference (no autograd).
@@ -200,8 +216,13 @@ def gcn_layer(lib, x, adj, w, bias, act, nbr=None, out=None, accumulate=False, p
     adj (TrussTopology.neighbor_table(), Kn <= 16) or None for a dense adjacency of at most 64 nodes; N <= 256.
     precision "bf16x3" (default): where the shape allows (the hidden layers: C > 32, K % 4 == 0, <= 9 terms per row) the product runs
     on the bf16 matrix cores as six partial products of exactly split operands with float32 accumulation -- float32 accuracy, 2.7 x
-    fewer matrix-core cycles; "f32": always the float32 matrix cores.  w_split: split_weights(lib, w) if the caller keeps it."""
+    fewer matrix-core cycles; "f32": always the float32 matrix cores.  "bf16x2" / "bf16": the same kernel on the first two terms /
+    the first term of both operands (`truss_gcn_layer_terms`; three products / one product): reduced precision for inference,
+    |out - ref64| <= (2^-13 + 1e-6) Mag / (2^-6 + 1e-6) Mag with Mag = |A| (|X| |W|^T) + |b| (+ |out0|), operands truncated (every
+    product biased towards zero); a layer outside that envelope runs in float32 as under every precision.
+    w_split: split_weights(lib, w) if the caller keeps it (one image serves all precisions)."""
     from . import ops
+    _check_precision(precision)
     B, N, K = x.shape
     C = w.shape[0]
     if out is None:
@@ -212,26 +233,34 @@ def gcn_layer(lib, x, adj, w, bias, act, nbr=None, out=None, accumulate=False, p
         adj = adj[0]
     code = {None: 0, "relu": 1, "sigmoid": 2}[act]
     ws = None
-    if precision == "bf16x3" and C > 32 and K % 4 == 0 and x.data_ptr() % 16 == 0 and (nbr.shape[1] if nbr is not None else N) <= 9:
+    if precision != "f32" and _bf16_envelope(x, w, nbr):
         ws = w_split if w_split is not None else split_weights(lib, w)
+    if ws is not None and precision != "bf16x3":
+        ops.call(ops.namespace().gcn_layer_terms, ops.bind(lib), ops.stream_of(x.device), x, adj, nbr, w, bias, out, code, ws, 0,
+                 None, None, None, None, 0, None, None, bool(accumulate), _BF16_TERMS[precision])
+        return out
     ops.call(ops.namespace().gcn_layer, ops.bind(lib), ops.stream_of(x.device), x, adj, nbr, w, bias, out, code, bool(accumulate), ws)
     return out
 
 
 def _gcn_layer_fused(lib, x, adj, w, bias, act, nbr, precision, w_split, out, kind, w2=None, bias2=None, adj2=None, nbr2=None, act2=None,
                      out2=None, pool=None):
-    """`truss_gcn_layer_fused`: the layer of `gcn_layer` with a consumer of its output in the epilogue of the same launch"""
+    """`truss_gcn_layer_fused`: the layer of `gcn_layer` with a consumer of its output in the epilogue of the same launch
+    (precision "bf16x2" / "bf16", inside the split-weight envelope: `truss_gcn_layer_terms` with the same epilogue)"""
     from . import ops
-    B, N, K = x.shape
-    C = w.shape[0]
+    _check_precision(precision)
     flat = lambda a: a[0] if a.dim() == 3 and a.shape[0] == 1 else a
     adj = flat(adj.contiguous())
     code = {None: 0, "relu": 1, "sigmoid": 2}
     ws = None
-    if precision == "bf16x3" and C > 32 and K % 4 == 0 and x.data_ptr() % 16 == 0 and (nbr.shape[1] if nbr is not None else N) <= 9:
+    if precision != "f32" and _bf16_envelope(x, w, nbr):
         ws = w_split if w_split is not None else split_weights(lib, w)
     if adj2 is not None:
         adj2 = flat(adj2.contiguous())
+    if ws is not None and precision != "bf16x3":
+        ops.call(ops.namespace().gcn_layer_terms, ops.bind(lib), ops.stream_of(x.device), x, adj, nbr, w, bias, out, code[act], ws, kind,
+                 w2, bias2, adj2, nbr2, code[act2], out2, pool, False, _BF16_TERMS[precision])
+        return
     ops.call(ops.namespace().gcn_layer_fused, ops.bind(lib), ops.stream_of(x.device), x, adj, nbr, w, bias, out, code[act], ws, kind,
              w2, bias2, adj2, nbr2, code[act2], out2, pool)
 
@@ -367,7 +396,7 @@ def path_graph_table(n_nodes):
     return t
 
 
-def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False):
+def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False, precision="bf16x3"):
     """truss2D_RL.multimodes_actor.forward (truss2D_RL.py:49-120) for inference, every GCN layer ONE launch of the fused MFMA
     kernel (`gcn_layer`: neighbourhood sum on the input rows, product with W^T on the matrix cores, bias + activation in the
     epilogue; H = X W never exists in HBM); the five second-level layers accumulate their sum x3 in place.  Same values as the
@@ -378,7 +407,11 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False):
     fused: the three activations that inference writes only to read them back once stay on chip (`truss_gcn_layer_fused`, 11 launches
     instead of 13): gcn_l1_4 is summed over the Pareto graph in its own epilogue (`gcn_layer_pool`), and the action heads gcn_l4_1 /
     gcn_l4_2 run in the epilogues of gcn_l3_1 / gcn_l3_2 (`gcn_layer_head`; they read lin.weight as it is).  Same values up to float32
-    summation order; a layer outside the kernel's envelope takes the unfused path."""
+    summation order; a layer outside the kernel's envelope takes the unfused path.
+    precision: handed to every layer (`gcn_layer`): "bf16x3" (default, float32 accuracy), "f32", or the reduced "bf16x2" / "bf16"
+    for the hidden layers -- the action heads and every other layer outside the split-weight envelope stay float32.  The cached
+    split weights (`layer_split_weights`) are the same for all of them."""
+    _check_precision(precision)
     x_n, A_n, A_s, A_ts, A_cs, x_p, A_p = ins
 
     def materialise(layer, x, a):                           # lazy layers: let the module materialise itself once
@@ -393,7 +426,7 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False):
         x = x.contiguous()
         if gcn_layer_supported(x.shape[1], w.shape[0], pat):
             wd, ws = layer_split_weights(lib, layer, x.shape[2])     # (x_n arrives zero-padded to 16 features)
-            return gcn_layer(lib, x, a, wd, bvec.detach(), act, pat, out, accumulate, w_split=ws)
+            return gcn_layer(lib, x, a, wd, bvec.detach(), act, pat, out, accumulate, precision=precision, w_split=ws)
         h = gcn_aggregate(lib, a, torch.nn.functional.linear(x, w).contiguous(), bvec, act, pat)
         if out is None:
             return h
@@ -406,7 +439,7 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False):
         if not (fused and gcn_layer_supported(x.shape[1], layer.lin.weight.shape[0], pat)):
             return g(layer, x, a).sum(dim=1)
         wd, ws = layer_split_weights(lib, layer, x.shape[2])
-        return gcn_layer_pool(lib, x, a, wd, layer.bias.detach(), "relu", pat, w_split=ws)
+        return gcn_layer_pool(lib, x, a, wd, layer.bias.detach(), "relu", pat, precision=precision, w_split=ws)
 
     def g_head(layer, head, x, a, a2):                      # g(head, g(layer, x, a), a2, "sigmoid") without the hidden tensor
         materialise(layer, x, a)
@@ -419,7 +452,8 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False):
                 and gcn_layer_supported(x.shape[1], w2.shape[0], pat2)):
             return g(head, g(layer, x, a), a2, "sigmoid")
         wd, ws = layer_split_weights(lib, layer, x.shape[2])
-        return gcn_layer_head(lib, x, a, wd, layer.bias.detach(), "relu", w2.detach(), head.bias.detach(), a2, "sigmoid", pat, pat2, w_split=ws)
+        return gcn_layer_head(lib, x, a, wd, layer.bias.detach(), "relu", w2.detach(), head.bias.detach(), a2, "sigmoid", pat, pat2,
+                              precision=precision, w_split=ws)
 
     a = actor
     if x_n.shape[2] % 4 and gcn_layer_supported(x_n.shape[1], 200, nbr):
@@ -640,8 +674,13 @@ class BatchedMARL:
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
                  pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None,
                  level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None,
-                 archive_path: str | None = None, actor_path: str | None = None):
-        """actor_path: how the rollout evaluates an actor -- "layers" (13 launches of the fused layer kernel, the default) or "fused"
+                 archive_path: str | None = None, actor_path: str | None = None, actor_precision: str | None = None):
+        """actor_precision: the product of the actors' hidden layers in the ROLLOUT (`actor_infer(precision=...)`): "bf16x3" (float32
+        accuracy, the default), "f32", or the reduced "bf16x2" / "bf16" (two terms / one term of the bf16 split, truncated: errors of
+        up to 2^-13 / 2^-6 of a layer's magnitude, every product biased towards zero; need a library with `truss_gcn_layer_terms`);
+        None: the environment's TRUSS_ACTOR_PRECISION, else "bf16x3".  Composes with actor_path; the update is not affected (it
+        evaluates the actors in float32 from the replayed states).
+        actor_path: how the rollout evaluates an actor -- "layers" (13 launches of the fused layer kernel, the default) or "fused"
         (`actor_infer(fused=True)`: the Pareto pool and the two action heads run in the epilogues of the layers that feed them, 11
         launches; needs a library with `truss_gcn_layer_fused`); None: "fused" if the environment has TRUSS_ACTOR=fused, else "layers".
         archive_path: how a game step updates the archives -- "torch" (candidate buffers, one `truss_front` launch and gathers by
@@ -723,6 +762,12 @@ class BatchedMARL:
         if actor_path == "fused" and not self.lib.has_gcn_fused:
             raise ValueError(f"actor_path='fused': {self.lib.path} has no truss_gcn_layer_fused")
         self.actor_path = actor_path
+        if actor_precision is None:
+            actor_precision = os.environ.get("TRUSS_ACTOR_PRECISION", "bf16x3")
+        _check_precision(actor_precision, "actor_precision")
+        if actor_precision in ("bf16x2", "bf16") and not self.lib.has_gcn_terms:
+            raise ValueError(f"actor_precision={actor_precision!r}: {self.lib.path} has no truss_gcn_layer_terms")
+        self.actor_precision = actor_precision
         self._arch_spare = None       # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
         if self.device.type == "cuda":
             import truss2D_RL
@@ -830,7 +875,7 @@ class BatchedMARL:
             for ag in self.rl.agents:
                 g, t = actor_infer(self.lib, ag.actor_model, [actor_in[0], self.A_n[0], actor_in[2], actor_in[3], actor_in[4],
                                                               actor_in[5], actor_in[6]], nbr=self.nbr, nbr_p=self.nbr_p,
-                                     fused=self.actor_path == "fused")
+                                     fused=self.actor_path == "fused", precision=self.actor_precision)
                 if explore:                                           # truss2D_RL.OUNoise.gen_noise per scalar (:41-48), all columns at once
                     for out, noises in ((g, ag.noise_geo), (t, ag.noise_topo)):
                         th_dt, mu, sg = self._noise_vectors(noises)
@@ -871,7 +916,8 @@ class BatchedMARL:
                 with torch.no_grad():
                     for ag_ in self.rl.agents:
                         actor_infer(self.lib, ag_.actor_model, [S[0][:1], self.A_n[0], S[2][:1], S[3][:1], S[4][:1], S[6][:1], S[7][:1]],
-                                    nbr=self.nbr, nbr_p=self.nbr_p, fused=self.actor_path == "fused")
+                                    nbr=self.nbr, nbr_p=self.nbr_p, fused=self.actor_path == "fused",
+                                    precision=self.actor_precision)
                 snap =[[p.detach().clone() for p in n.parameters()] for n in nets]
                 osnap = [t.clone() for t in self.rl.critics_opt.state_tensors()]    # [] = no step taken yet (one optimiser for the three critics)
                 n_loss = [len(ag_.c_loss) for ag_ in self.rl.agents]

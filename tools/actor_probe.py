@@ -11,7 +11,13 @@ has to exceed), and the largest difference between the two paths' outputs.  "lau
 each path with torch.profiler (a run of its own: tracing slows the host) and lists, with their device time, the three fused launches
 next to the launches they replace (the 200 -> 200 layers that feed the heads, the heads, the Pareto layer and the reduction).
 Shapes: the reference's actor (hidden 200, heads 2 and 3) at the small_roof widths (16 nodes), 4096 and 14 336 (env, member) pairs
-with a Pareto graph of 20 members (the train game) and 4096 pairs with 50 members (the design game)."""
+with a Pareto graph of 20 members (the train game) and 4096 pairs with 50 members (the design game).
+
+    python tools/actor_probe.py --precision [OUT_DIR]   -> OUT_DIR/actor_precision.json
+
+times actor_infer(precision=...) instead (one child process): per shape (4096 and 14 336 pairs, P 20), actor path (layers, fused) and
+reduced precision T ("bf16x2", "bf16"), medians of 60 synchronised calls in alternating blocks  bf16x3, T, bf16x3 again,  and the
+largest deviation of T's action tensors from the bf16x3 ones."""
 import json
 import os
 import statistics
@@ -98,6 +104,47 @@ def child_time():
     print(json.dumps(out))
 
 
+def child_precision():
+    import torch
+    import truss_mi355 as tm
+    from truss_mi355 import marl
+    dev = torch.device("cuda")
+    lib = tm.load()
+    out = {}
+    for label, B, P in SHAPES[:2]:
+        actor, ins, kw = setup(B, P, dev)
+
+        def times(f, n):
+            ts = []
+            for _ in range(n):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                f()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e6)
+            return ts
+
+        for fused in (False, True):
+            def run(precision, fused=fused):
+                with torch.no_grad():
+                    return marl.actor_infer(lib, actor, ins, fused=fused, precision=precision, **kw)
+            for p in ("bf16x3", "bf16x2", "bf16"):
+                times(lambda: run(p), 10)
+            for p in ("bf16x2", "bf16"):
+                ts = {"bf16x3": [], p: [], "bf16x3_again": []}
+                for _ in range(ROUNDS):
+                    for k in ts:
+                        ts[k] += times(lambda: run("bf16x3" if k.startswith("bf16x3") else p), BLOCK)
+                a, b = run("bf16x3"), run(p)
+                out[f"{label} path={'fused' if fused else 'layers'} {p}"] = {
+                    "call_us": {k: round(statistics.median(v), 1) for k, v in ts.items()}, "calls_per_median": ROUNDS * BLOCK,
+                    "max_abs_deviation_from_bf16x3": max(float((x - y).abs().max()) for x, y in zip(a, b)),
+                    "mean_signed_deviation": [float((y - x).double().mean()) for x, y in zip(a, b)]}
+        del actor, ins, kw
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def child_launches():
     import torch
     from torch.profiler import profile, ProfilerActivity
@@ -141,7 +188,10 @@ def main():
     me = os.path.abspath(__file__)
     env = dict(os.environ, TMPDIR="/tmp")
     result = {}
-    for step, limit in (("time", "300"), ("launches", "180")):
+    precision = "--precision" in sys.argv[1:2]
+    if precision:
+        out_dir = os.path.abspath(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "actor_probe"))
+    for step, limit in ((("precision", "300"),) if precision else (("time", "300"), ("launches", "180"))):
         p = subprocess.run(["timeout", "-k", "10", limit, sys.executable, me, "--child", step], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True)
         with open(os.path.join(out_dir, step + ".err"), "w") as f:
@@ -150,13 +200,13 @@ def main():
             print(f"the {step} step failed with status {p.returncode}\n{p.stderr[-2000:]}", file=sys.stderr)
             sys.exit(1)
         result[step] = json.loads(p.stdout.strip().splitlines()[-1])
-        with open(os.path.join(out_dir, "actor_probe.json"), "w") as f:
+        with open(os.path.join(out_dir, "actor_precision.json" if precision else "actor_probe.json"), "w") as f:
             json.dump(result, f, indent=1)
     print(json.dumps(result, indent=1))
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        {"time": child_time, "launches": child_launches}[sys.argv[2]]()
+        {"time": child_time, "launches": child_launches, "precision": child_precision}[sys.argv[2]]()
     else:
         main()
