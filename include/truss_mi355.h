@@ -475,6 +475,33 @@ int truss_gcn_layer_fused(const truss_gcn_layer_args_t *layer, const truss_gcn_e
  * capturable; bitwise reproducible.  Optional entry of ABI version 3 (a library may lack it). */
 int truss_gcn_layer_terms(const truss_gcn_layer_args_t *layer, const truss_gcn_epilogue_t *epi, int32_t bf16_terms, void *stream);
 
+/* SEVERAL split-weight layers in ONE launch: the layers of one depth of the actors' inference, for all agents (truss2D_RL.py:86-120
+ * evaluated for three actors that read the same observations: 9 input layers, 3 Pareto layers, 3 x 5 second-level layers, 6 head
+ * layers).  layers is [n_chains][steps_per_chain]; the result is that of
+ *   truss_gcn_layer_terms(&layers[c * S + s], s == S - 1 && epis ? &epis[c] : NULL, bf16_terms, stream)
+ * for c = 0 .. n_chains - 1, s = 0 .. S - 1 (S = steps_per_chain) in that order, BIT FOR BIT: every output element is computed by
+ * the same instructions in the same order; only which workgroup runs which layer differs.  Grid = (row tiles, chains): a workgroup
+ * owns one row tile of one chain and runs the chain's steps one after the other.
+ *   chains  do not depend on each other: no output (out, out2, pool) of one chain may overlap anything another chain reads or
+ *           writes (TRUSS_EINVAL).
+ *   steps   of a chain write the same out (out, out_row_stride and c_out agree), each with its own accumulate flag: the five
+ *           second-level layers of an actor, which add into one tensor.  A step accumulates onto what the SAME THREAD stored in
+ *           the step before.  No step may read, as its x, rows of the chain's out (TRUSS_EINVAL): those would be rows other
+ *           threads wrote.  k_in, act, accumulate, adj / a_batch_stride / nbr, w, bias and x may differ from step to step.
+ *   epis    NULL, or one epilogue per chain, all of one kind; then steps_per_chain must be 1.
+ * All layers share n_batch, n_nodes, table-or-dense and the kernel instantiation truss_gcn_layer_terms would choose for them (at
+ * most 6 terms per row, or 7..9) -- TRUSS_EINVAL otherwise -- and each passes every check of truss_gcn_layer_terms, with that
+ * entry's codes.  TRUSS_EINVAL as well: n_chains < 0, steps_per_chain < 1, more than TRUSS_GCN_GROUP_MAX_STEPS layers, more than
+ * TRUSS_GCN_GROUP_MAX_EPI chains with epilogues, bf16_terms outside 1..3.  n_chains == 0 or n_batch == 0: TRUSS_OK, no launch.
+ * The layers' descriptors travel in the kernel arguments: the entry allocates nothing, copies nothing, does not synchronise and
+ * launches nothing and writes nothing on any refusal; capturable; bitwise reproducible.  Optional entry of ABI version 3 (a
+ * library may lack it). */
+#define TRUSS_GCN_GROUP_MAX_STEPS 16   /* n_chains * steps_per_chain, plain layers */
+#define TRUSS_GCN_GROUP_MAX_EPI    8   /* n_chains when epilogues are given */
+int truss_gcn_layer_group(const truss_gcn_layer_args_t *layers,   /* [n_chains][steps_per_chain] */
+                          const truss_gcn_epilogue_t *epis,       /* NULL, or [n_chains] */
+                          int32_t n_chains, int32_t steps_per_chain, int32_t bf16_terms, void *stream);
+
 /* A whole LEVEL of GCN layers in one launch: layers[i] as for truss_gcn_layer, for n_layers layers that do not depend on each other
  * -- the layers of one depth of the reference's actor / critic graphs (truss2D_RL.py:86-103, 116-133), of one network or of
  * several.  replaces: the forward passes of the MADDPG update (truss2D_RL.py:561-629: 19 network passes of 13 / 21 GCN layers at

@@ -483,6 +483,7 @@ extern "C" int truss_debug_stamps(unsigned long long *out16) {
 #endif
 
 #include "truss_gcn.h"
+#include "truss_gcn_group.h"
 #include "truss_gcn_level.h"
 #include "truss_gcn_level_bwd.h"
 #include "truss_replay.h"

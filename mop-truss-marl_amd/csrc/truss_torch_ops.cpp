@@ -40,7 +40,8 @@
   X(reward, truss_reward, false)                                 \
   X(archive_merge, truss_archive_merge, false)                   \
   X(gcn_layer_fused, truss_gcn_layer_fused, false)               \
-  X(gcn_layer_terms, truss_gcn_layer_terms, false)
+  X(gcn_layer_terms, truss_gcn_layer_terms, false)               \
+  X(gcn_layer_group, truss_gcn_layer_group, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -362,6 +363,43 @@ void gcn_layer_terms(int64_t lib, int64_t stream, const at::Tensor &x, const at:
   a.accumulate = accumulate ? 1 : 0;
   TORCH_CHECK(terms >= INT32_MIN && terms <= INT32_MAX, "truss_mi355: gcn_layer_terms: terms out of range");
   check_rc(b, b.gcn_layer_terms(&a, kind == 0 ? nullptr : &e, (int32_t)terms, (void *)stream), "truss_gcn_layer_terms");
+}
+
+// several split-weight layers in one launch: the lists hold one entry per layer, chain-major ([n_chains][steps_per_chain]); layer i
+// is what gcn_layer_terms takes.  kind 0: plain layers (out required, the epilogue lists empty); kind 1 / 2: one step per chain, each
+// with the epilogue of gcn_layer_fused (out optional) == truss_gcn_layer_group
+void gcn_layer_group(int64_t lib, int64_t stream, at::TensorList x, at::TensorList adj, const c10::List<OT> &nbr, at::TensorList w,
+                     const c10::List<OT> &bias, const c10::List<OT> &out, at::IntArrayRef act, const c10::List<bool> &accumulate,
+                     at::TensorList w_split, int64_t steps_per_chain, int64_t kind, const c10::List<OT> &w2, const c10::List<OT> &bias2,
+                     const c10::List<OT> &adj2, const c10::List<OT> &nbr2, at::IntArrayRef act2, const c10::List<OT> &out2,
+                     const c10::List<OT> &pool, int64_t terms) {
+  const Backend &b = backend(lib);
+  need(b.gcn_layer_group, "truss_gcn_layer_group");
+  const size_t L = x.size();
+  auto per_layer = [L](const c10::List<OT> &l) { return l.empty() || l.size() == L; };
+  TORCH_CHECK(adj.size() == L && w.size() == L && act.size() == L && accumulate.size() == L && w_split.size() == L && per_layer(nbr) &&
+                  per_layer(bias) && out.size() == L,
+              "truss_mi355: gcn_layer_group takes one entry per layer in every list");
+  TORCH_CHECK(kind != 0 ? (per_layer(w2) && per_layer(bias2) && per_layer(adj2) && per_layer(nbr2) && act2.size() == L && per_layer(out2) &&
+                           per_layer(pool))
+                        : (w2.empty() && bias2.empty() && adj2.empty() && nbr2.empty() && act2.empty() && out2.empty() && pool.empty()),
+              "truss_mi355: gcn_layer_group: the epilogue lists hold one entry per layer, or are empty without an epilogue (kind 0)");
+  TORCH_CHECK(steps_per_chain >= INT32_MIN && steps_per_chain <= INT32_MAX && terms >= INT32_MIN && terms <= INT32_MAX && L <= INT32_MAX,
+              "truss_mi355: gcn_layer_group: steps_per_chain / terms out of range");
+  TORCH_CHECK(steps_per_chain < 1 || L % (size_t)steps_per_chain == 0, "truss_mi355: gcn_layer_group: ", L, " layers are not whole chains of ",
+              steps_per_chain);
+  std::vector<truss_gcn_layer_args_t> args(L);
+  std::vector<truss_gcn_epilogue_t> epi(L);
+  for (size_t i = 0; i < L; ++i) {
+    fused_args(b, args[i], epi[i], x[i], adj[i], at_or_none(nbr, i), w[i], at_or_none(bias, i), out.get(i), act[i], OT(w_split[i]), kind,
+               at_or_none(w2, i), at_or_none(bias2, i), at_or_none(adj2, i), at_or_none(nbr2, i), kind != 0 ? act2[i] : 0, at_or_none(out2, i),
+               at_or_none(pool, i));
+    TORCH_CHECK(kind != 0 || present(out.get(i)), "truss_mi355: gcn_layer_group: out must be [B, N, C] for a plain layer (kind 0)");
+    args[i].accumulate = accumulate.get(i) ? 1 : 0;
+  }
+  const int32_t chains = steps_per_chain >= 1 ? (int32_t)(L / (size_t)steps_per_chain) : (int32_t)L;
+  check_rc(b, b.gcn_layer_group(args.data(), kind == 0 ? nullptr : epi.data(), chains, (int32_t)steps_per_chain, (int32_t)terms, (void *)stream),
+           "truss_gcn_layer_group");
 }
 
 // a whole level of GCN layers in one launch: out[i] = act[i](adj[i] @ (x[i] @ w[i]^T) + bias[i]); x_agg (empty, or one tensor per
@@ -694,6 +732,9 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("gcn_layer_terms(int lib, int stream, Tensor x, Tensor adj, Tensor? nbr, Tensor w, Tensor? bias, Tensor(a!)? out, int act, Tensor? w_split, "
         "int kind, Tensor? w2, Tensor? bias2, Tensor? adj2, Tensor? nbr2, int act2, Tensor(b!)? out2, Tensor(c!)? pool, bool accumulate, "
         "int terms) -> ()");
+  m.def("gcn_layer_group(int lib, int stream, Tensor[] x, Tensor[] adj, Tensor?[] nbr, Tensor[] w, Tensor?[] bias, Tensor(a!)?[] out, int[] act, "
+        "bool[] accumulate, Tensor[] w_split, int steps_per_chain, int kind, Tensor?[] w2, Tensor?[] bias2, Tensor?[] adj2, Tensor?[] nbr2, "
+        "int[] act2, Tensor(b!)?[] out2, Tensor(c!)?[] pool, int terms) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

@@ -119,6 +119,7 @@ _LATER_ENTRIES = [
     ("truss_archive_merge", [C.POINTER(ArchiveArgs), _vp]),
     ("truss_gcn_layer_fused", [_vp, _vp, _vp]),
     ("truss_gcn_layer_terms", [_vp, _vp, _i32, _vp]),
+    ("truss_gcn_layer_group", [_vp, _vp, _i32, _i32, _i32, _vp]),
 ]
 
 
@@ -154,6 +155,7 @@ class TrussLib:
         self.has_archive = "truss_archive_merge" in found                                    # the fused archive update
         self.has_gcn_fused = "truss_gcn_layer_fused" in found                                # a GCN layer with its consumer in the epilogue
         self.has_gcn_terms = "truss_gcn_layer_terms" in found                                # the split-weight layer on one or two bf16 terms
+        self.has_gcn_group = "truss_gcn_layer_group" in found                                # several split-weight layers in one launch
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")
         self.backend = d.truss_backend().decode()

@@ -413,6 +413,31 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False, precision="b
     split weights (`layer_split_weights`) are the same for all of them."""
     _check_precision(precision)
     x_n, A_n, A_s, A_ts, A_cs, x_p, A_p = ins
+    materialise, g, g_pool, g_head = _actor_layer_calls(lib, A_p, nbr, nbr_p, fused, precision)
+    a = actor
+    if x_n.shape[2] % 4 and gcn_layer_supported(x_n.shape[1], 200, nbr):
+        # 13 node features -> 16 (zero columns, matched by zero columns of the three input kernels): 16-byte loads, bf16x3 product
+        for layer in (a.gcn_l1_1, a.gcn_l1_2, a.gcn_l1_3):
+            materialise(layer, x_n, A_n)
+        x_n = torch.nn.functional.pad(x_n, (0, 4 - x_n.shape[2] % 4))
+    x11, x12, x13 = g(a.gcn_l1_1, x_n, A_n), g(a.gcn_l1_2, x_n, A_n), g(a.gcn_l1_3, x_n, A_n)
+    x14 = g_pool(a.gcn_l1_4, x_p, A_p)                                                   # GlobalSumPool over the Pareto graph
+    B, H = x14.shape
+    x14 = x14.unsqueeze(-1).expand(B, H, x11.shape[1]).reshape(B, x11.shape[1], H)      # _tile_pool (:87-93)
+    x3 = g(a.gcn_l2_1, x11, A_n)
+    g(a.gcn_l2_2, x12, A_ts, out=x3, accumulate=True)
+    g(a.gcn_l2_3, x12, A_cs, out=x3, accumulate=True)
+    g(a.gcn_l2_4, x13, A_s, out=x3, accumulate=True)
+    g(a.gcn_l2_5, x14.contiguous(), A_n, out=x3, accumulate=True)
+    if not fused:
+        x31, x32 = g(a.gcn_l3_1, x3, A_n), g(a.gcn_l3_2, x3, A_s)
+        return g(a.gcn_l4_1, x31, A_n, "sigmoid"), g(a.gcn_l4_2, x32, A_n, "sigmoid")
+    materialise(a.gcn_l3_1, x3, A_n), materialise(a.gcn_l3_2, x3, A_s)                  # (lazy layers: in the order of the unfused path)
+    return g_head(a.gcn_l3_1, a.gcn_l4_1, x3, A_n, A_n), g_head(a.gcn_l3_2, a.gcn_l4_2, x3, A_s, A_n)
+
+
+def _actor_layer_calls(lib, A_p, nbr, nbr_p, fused, precision):
+    """the per-layer calls of `actor_infer` (and of the levels `actors_infer` does not group): (materialise, g, g_pool, g_head)"""
 
     def materialise(layer, x, a):                           # lazy layers: let the module materialise itself once
         if isinstance(layer.lin.weight, torch.nn.parameter.UninitializedParameter):
@@ -455,28 +480,156 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False, precision="b
         return gcn_layer_head(lib, x, a, wd, layer.bias.detach(), "relu", w2.detach(), head.bias.detach(), a2, "sigmoid", pat, pat2,
                               precision=precision, w_split=ws)
 
-    a = actor
-    if x_n.shape[2] % 4 and gcn_layer_supported(x_n.shape[1], 200, nbr):
-        # 13 node features -> 16 (zero columns, matched by zero columns of the three input kernels): 16-byte loads, bf16x3 product
+    return materialise, g, g_pool, g_head
+
+
+_ACT_CODE = {None: 0, "relu": 1, "sigmoid": 2}
+GROUP_MAX_STEPS, GROUP_MAX_EPI = 16, 8                      # TRUSS_GCN_GROUP_MAX_STEPS / _EPI (include/truss_mi355.h)
+
+
+def gcn_layer_group(lib, chains, precision="bf16x3", epilogues=None):
+    """Several split-weight GCN layers in ONE launch (`truss_gcn_layer_group`, csrc/truss_gcn_group.h): the same bits as running them
+    one by one through `gcn_layer` / `gcn_layer_head` / `gcn_layer_pool` in chain order.
+    chains: a list of chains of equal length; a chain is a list of steps that write the same `out`, a step a dict with the arguments of
+    `gcn_layer` by name: x, adj, w, bias, act, out, w_split (required: `split_weights(lib, w)`), and optionally nbr, accumulate.
+    Chains must not depend on each other; a step must not read the chain's `out`.  All layers share B, N and table-or-dense.
+    epilogues: None, or one dict per chain (chains of one step; out may then be None): kind "head" with w2, bias2, adj2, act2, out2
+    and optionally nbr2, or kind "pool" with pool -- all of one kind.
+    precision: "bf16x3", "bf16x2" or "bf16" (this entry is the split-weight path only: no "f32", and a layer outside the
+    split-weight envelope is refused by the library, not rerouted).  At most 16 plain layers, or 8 chains with epilogues."""
+    from . import ops
+    _check_precision(precision)
+    if precision == "f32":
+        raise ValueError("gcn_layer_group is the split-weight path: precision must be 'bf16x3', 'bf16x2' or 'bf16'")
+    flat = lambda a: None if a is None else (lambda c: c[0] if c.dim() == 3 and c.shape[0] == 1 else c)(a.contiguous())
+    steps = [s for chain in chains for s in chain]
+    per_chain = len(chains[0]) if chains else 1
+    assert all(len(chain) == per_chain for chain in chains) and (epilogues is None or len(epilogues) == len(chains))
+    col = lambda key, default=None: [s.get(key, default) for s in steps]
+    kind, epi = 0, [[] for _ in range(7)]
+    if epilogues is not None:
+        kinds = {e["kind"] for e in epilogues}
+        assert len(kinds) <= 1 and kinds <= {"head", "pool"}, "epilogues of one kind, 'head' or 'pool'"
+        kind = 1 if kinds == {"head"} else 2
+        ecol = lambda key: [e.get(key) for e in epilogues]
+        epi = [ecol("w2"), ecol("bias2"), [flat(a) for a in ecol("adj2")], ecol("nbr2"), [_ACT_CODE[e.get("act2")] for e in epilogues],
+               ecol("out2"), ecol("pool")]
+    device = steps[0]["x"].device if steps else torch.device("cpu")
+    ops.call(ops.namespace().gcn_layer_group, ops.bind(lib), ops.stream_of(device), col("x"), [flat(a) for a in col("adj")], col("nbr"),
+             col("w"), col("bias"), col("out"), [_ACT_CODE[s["act"]] for s in steps], [bool(s.get("accumulate", False)) for s in steps],
+             col("w_split"), per_chain, kind, *epi, _BF16_TERMS[precision])
+
+
+def actors_infer(lib, actors, ins, nbr=None, nbr_p=None, precision="bf16x3"):
+    """`actor_infer(fused=True)` for EVERY actor of `actors` on the same inputs, level by level: [(geo_a, topo_a) for a in actors],
+    bit for bit what the per-actor calls return.  The actors read the same observation tensors and their layers have the same
+    shapes; within an actor the layers of one depth do not depend on each other.  So each depth is one launch of
+    `truss_gcn_layer_group` for all actors -- the 3 A input layers; the A Pareto layers with the pool epilogue into one [A, B, H]
+    buffer, tiled by one copy; A chains of the five second-level layers, which accumulate x3 in place; the 2 A layers that feed
+    the heads, with the head epilogue -- four launches and three framework kernels (the pad of x_n, the tiling copy, and
+    contiguous() where an input needs it) instead of 11 A launches and 3 A framework kernels.
+    A level with a layer outside the split-weight envelope (precision "f32", a node graph without a table or with more than nine
+    terms per row, a head wider than 8, a library without the entry) runs through the per-layer calls of `actor_infer`; only
+    that level does.  Lazy layers are materialised actor by actor in the order of the unfused path; the cached weight images are
+    those of `layer_split_weights`."""
+    _check_precision(precision)
+    x_n, A_n, A_s, A_ts, A_cs, x_p, A_p = ins
+    materialise, g, g_pool, g_head = _actor_layer_calls(lib, A_p, nbr, nbr_p, True, precision)
+    A, N = len(actors), x_n.shape[1]
+    if A == 0:
+        return []
+    for a in actors:                                        # lazy layers, in the order consecutive actor_infer calls materialise them
         for layer in (a.gcn_l1_1, a.gcn_l1_2, a.gcn_l1_3):
-            if isinstance(layer.lin.weight, torch.nn.parameter.UninitializedParameter):
-                with torch.no_grad():
-                    layer(x_n[:1], A_n[:1] if A_n.dim() == 3 else A_n)
-        x_n = torch.nn.functional.pad(x_n, (0, 4 - x_n.shape[2] % 4))
-    x11, x12, x13 = g(a.gcn_l1_1, x_n, A_n), g(a.gcn_l1_2, x_n, A_n), g(a.gcn_l1_3, x_n, A_n)
-    x14 = g_pool(a.gcn_l1_4, x_p, A_p)                                                   # GlobalSumPool over the Pareto graph
-    B, H = x14.shape
-    x14 = x14.unsqueeze(-1).expand(B, H, x11.shape[1]).reshape(B, x11.shape[1], H)      # _tile_pool (:87-93)
-    x3 = g(a.gcn_l2_1, x11, A_n)
-    g(a.gcn_l2_2, x12, A_ts, out=x3, accumulate=True)
-    g(a.gcn_l2_3, x12, A_cs, out=x3, accumulate=True)
-    g(a.gcn_l2_4, x13, A_s, out=x3, accumulate=True)
-    g(a.gcn_l2_5, x14.contiguous(), A_n, out=x3, accumulate=True)
-    if not fused:
-        x31, x32 = g(a.gcn_l3_1, x3, A_n), g(a.gcn_l3_2, x3, A_s)
-        return g(a.gcn_l4_1, x31, A_n, "sigmoid"), g(a.gcn_l4_2, x32, A_n, "sigmoid")
-    materialise(a.gcn_l3_1, x3, A_n), materialise(a.gcn_l3_2, x3, A_s)                  # (lazy layers: in the order of the unfused path)
-    return g_head(a.gcn_l3_1, a.gcn_l4_1, x3, A_n, A_n), g_head(a.gcn_l3_2, a.gcn_l4_2, x3, A_s, A_n)
+            materialise(layer, x_n, A_n)
+        materialise(a.gcn_l1_4, x_p, A_p)
+        lazy = lambda layer: isinstance(layer.lin.weight, torch.nn.parameter.UninitializedParameter)
+        for layer, src, adj in ((a.gcn_l2_1, a.gcn_l1_1, A_n), (a.gcn_l2_2, a.gcn_l1_2, A_ts), (a.gcn_l2_3, a.gcn_l1_2, A_cs),
+                                (a.gcn_l2_4, a.gcn_l1_3, A_s), (a.gcn_l2_5, a.gcn_l1_4, A_n), (a.gcn_l3_1, a.gcn_l2_1, A_n),
+                                (a.gcn_l3_2, a.gcn_l2_1, A_s), (a.gcn_l4_1, a.gcn_l3_1, A_n), (a.gcn_l4_2, a.gcn_l3_2, A_n)):
+            if lazy(layer):                                 # (the layer's input matters by its width only)
+                materialise(layer, x_n.new_zeros((1, N, src.lin.weight.shape[0])), adj)
+    if x_n.shape[2] % 4 and gcn_layer_supported(N, 200, nbr):
+        x_n = torch.nn.functional.pad(x_n, (0, 4 - x_n.shape[2] % 4))          # once for all actors
+    x_n, x_p = x_n.contiguous(), x_p.contiguous()
+    can_group = lib.has_gcn_group and precision != "f32"
+
+    def step(layer, x, adj, pat, out=None, accumulate=False):
+        """the layer as a step of `gcn_layer_group`, or None outside the envelope of the grouped launch"""
+        if not gcn_layer_supported(x.shape[1], layer.lin.weight.shape[0], pat):
+            return None
+        wd, ws = layer_split_weights(lib, layer, x.shape[2])
+        if ws is None or not _bf16_envelope(x, wd, pat):
+            return None
+        return dict(x=x, adj=adj, nbr=pat, w=wd, bias=layer.bias.detach(), act="relu", out=out, accumulate=accumulate, w_split=ws)
+
+    def launch(chains, epilogues, limit):
+        """one launch, or one per `limit` chains where the actors are many"""
+        for i in range(0, len(chains), limit):
+            gcn_layer_group(lib, chains[i:i + limit], precision, None if epilogues is None else epilogues[i:i + limit])
+
+    def outputs(n, shape):
+        return list(torch.empty((n,) + tuple(shape), dtype=torch.float32, device=x_n.device).unbind(0))
+
+    B = x_n.shape[0]
+    # depth 1, node graph: gcn_l1_1 .. gcn_l1_3 of every actor
+    firsts = [(a.gcn_l1_1, a.gcn_l1_2, a.gcn_l1_3) for a in actors]
+    steps = [step(layer, x_n, A_n, nbr) for trio in firsts for layer in trio] if can_group else [None]
+    widths = {s["w"].shape[0] for s in steps if s is not None}
+    if all(s is not None for s in steps) and len(widths) == 1:
+        for s, o in zip(steps, outputs(len(steps), (B, N, widths.pop()))):
+            s["out"] = o
+        launch([[s] for s in steps], None, GROUP_MAX_STEPS)
+        x1 = [[steps[3 * i + j]["out"] for j in range(3)] for i in range(A)]
+    else:
+        x1 = [[g(layer, x_n, A_n) for layer in trio] for trio in firsts]
+    # depth 1, Pareto graph: gcn_l1_4 summed over the front's members, tiled over the nodes (_tile_pool, truss2D_RL.py:87-93)
+    steps = [step(a.gcn_l1_4, x_p, A_p, nbr_p) for a in actors] if can_group else [None]
+    widths = {s["w"].shape[0] for s in steps if s is not None}
+    if all(s is not None for s in steps) and len(widths) == 1:
+        H = widths.pop()
+        pooled = torch.empty((A, B, H), dtype=torch.float32, device=x_n.device)
+        launch([[s] for s in steps], [dict(kind="pool", pool=pooled[i]) for i in range(A)], GROUP_MAX_EPI)
+        x14 = list(pooled.unsqueeze(-1).expand(A, B, H, N).reshape(A, B, N, H).unbind(0))     # one copy for all actors
+    else:
+        x14 = []
+        for a in actors:
+            p = g_pool(a.gcn_l1_4, x_p, A_p)
+            x14.append(p.unsqueeze(-1).expand(p.shape[0], p.shape[1], N).reshape(p.shape[0], N, p.shape[1]).contiguous())
+    # depth 2: five layers per actor that add into x3, in the order of actor_infer
+    def seconds(a, x, x4, out):
+        return [(a.gcn_l2_1, x[0], A_n, out, False), (a.gcn_l2_2, x[1], A_ts, out, True), (a.gcn_l2_3, x[1], A_cs, out, True),
+                (a.gcn_l2_4, x[2], A_s, out, True), (a.gcn_l2_5, x4, A_n, out, True)]
+    widths = {a.gcn_l2_1.lin.weight.shape[0] for a in actors}
+    chains = None
+    if can_group and len(widths) == 1:
+        x3 = outputs(A, (B, N, widths.pop()))
+        chains = [[step(layer, x.contiguous(), adj, nbr, out, acc) for layer, x, adj, out, acc in seconds(a, x1[i], x14[i], x3[i])]
+                  for i, a in enumerate(actors)]
+        if not all(s is not None and s["w"].shape[0] == s["out"].shape[2] for chain in chains for s in chain):
+            chains = None
+    if chains is not None:
+        launch(chains, None, GROUP_MAX_STEPS // 5)
+    else:
+        x3 = []
+        for i, a in enumerate(actors):
+            calls = seconds(a, x1[i], x14[i], None)
+            out = g(*calls[0][:3])
+            for layer, x, adj, _, _ in calls[1:]:
+                g(layer, x, adj, out=out, accumulate=True)
+            x3.append(out)
+    # depths 3 + 4: gcn_l3_1 + gcn_l4_1 over A_n, gcn_l3_2 over A_s with gcn_l4_2 over A_n
+    pairs = [(layer, head, adj, x3[i]) for i, a in enumerate(actors)
+             for layer, head, adj in ((a.gcn_l3_1, a.gcn_l4_1, A_n), (a.gcn_l3_2, a.gcn_l4_2, A_s))]
+    steps = [step(layer, x, adj, nbr) for layer, _, adj, x in pairs] if can_group else [None]
+    if all(s is not None for s in steps) and all(head.lin.weight.shape[0] <= 8 and gcn_layer_supported(N, head.lin.weight.shape[0], nbr)
+                                                  for _, head, _, _ in pairs):
+        epis = [dict(kind="head", w2=head.lin.weight.detach(), bias2=head.bias.detach(), adj2=A_n, nbr2=nbr, act2="sigmoid",
+                     out2=torch.empty((B, N, head.lin.weight.shape[0]), dtype=torch.float32, device=x_n.device)) for _, head, _, _ in pairs]
+        launch([[s] for s in steps], epis, GROUP_MAX_EPI)
+        heads = [e["out2"] for e in epis]
+    else:
+        heads = [g_head(layer, head, x, adj, A_n) for layer, head, adj, x in pairs]
+    return [(heads[2 * i], heads[2 * i + 1]) for i in range(A)]
 
 
 class DeviceReplay:
@@ -682,7 +835,9 @@ class BatchedMARL:
         evaluates the actors in float32 from the replayed states).
         actor_path: how the rollout evaluates an actor -- "layers" (13 launches of the fused layer kernel, the default) or "fused"
         (`actor_infer(fused=True)`: the Pareto pool and the two action heads run in the epilogues of the layers that feed them, 11
-        launches; needs a library with `truss_gcn_layer_fused`); None: "fused" if the environment has TRUSS_ACTOR=fused, else "layers".
+        launches; needs a library with `truss_gcn_layer_fused`) or "grouped" (`actors_infer`: the fused path for all three actors at
+        once, every depth of their layers ONE launch of `truss_gcn_layer_group` -- four launches per call instead of 33, the same bits
+        as "fused"; needs a library with that entry); None: the environment's TRUSS_ACTOR if it is "fused" or "grouped", else "layers".
         archive_path: how a game step updates the archives -- "torch" (candidate buffers, one `truss_front` launch and gathers by
         framework operators, the default) or "hip" (one `truss_archive_merge` launch per chunk, per step in the design game; needs a
         library with that entry; the archive then lives in two sets of buffers that swap roles); None: "hip" if the environment has
@@ -756,11 +911,14 @@ class BatchedMARL:
                                  f"{_lib.ARCHIVE_MAXROWS} rows of truss_archive_merge")
         self.archive_path = archive_path
         if actor_path is None:
-            actor_path = "fused" if os.environ.get("TRUSS_ACTOR", "layers") == "fused" else "layers"
-        if actor_path not in ("layers", "fused"):
-            raise ValueError(f"actor_path must be 'layers' or 'fused', got {actor_path!r}")
-        if actor_path == "fused" and not self.lib.has_gcn_fused:
-            raise ValueError(f"actor_path='fused': {self.lib.path} has no truss_gcn_layer_fused")
+            actor_path = os.environ.get("TRUSS_ACTOR", "layers")
+            actor_path = actor_path if actor_path in ("fused", "grouped") else "layers"
+        if actor_path not in ("layers", "fused", "grouped"):
+            raise ValueError(f"actor_path must be 'layers', 'fused' or 'grouped', got {actor_path!r}")
+        if actor_path == "grouped" and not self.lib.has_gcn_group:
+            raise ValueError(f"actor_path='grouped': {self.lib.path} has no truss_gcn_layer_group")
+        if actor_path in ("fused", "grouped") and not self.lib.has_gcn_fused:       # (a level outside the group's envelope runs fused)
+            raise ValueError(f"actor_path={actor_path!r}: {self.lib.path} has no truss_gcn_layer_fused")
         self.actor_path = actor_path
         if actor_precision is None:
             actor_precision = os.environ.get("TRUSS_ACTOR_PRECISION", "bf16x3")
@@ -871,12 +1029,17 @@ class BatchedMARL:
         ins = self._net_state(S)
         actor_in = [ins[0], ins[1], ins[2], ins[3], ins[4], ins[6], ins[7]]
         geo, topo = [], []
+        net_in = [actor_in[0], self.A_n[0], actor_in[2], actor_in[3], actor_in[4], actor_in[5], actor_in[6]]
         with torch.no_grad():
-            for ag in self.rl.agents:
-                g, t = actor_infer(self.lib, ag.actor_model, [actor_in[0], self.A_n[0], actor_in[2], actor_in[3], actor_in[4],
-                                                              actor_in[5], actor_in[6]], nbr=self.nbr, nbr_p=self.nbr_p,
-                                     fused=self.actor_path == "fused", precision=self.actor_precision)
-                if explore:                                           # truss2D_RL.OUNoise.gen_noise per scalar (:41-48), all columns at once
+            grouped = None
+            if self.actor_path == "grouped":                          # every actor's layers of a depth in one launch, before any noise
+                grouped = actors_infer(self.lib, [ag.actor_model for ag in self.rl.agents], net_in, nbr=self.nbr, nbr_p=self.nbr_p,
+                                       precision=self.actor_precision)
+            for i, ag in enumerate(self.rl.agents):
+                g, t = grouped[i] if grouped is not None else actor_infer(
+                    self.lib, ag.actor_model, net_in, nbr=self.nbr, nbr_p=self.nbr_p, fused=self.actor_path == "fused",
+                    precision=self.actor_precision)
+                if explore:                                          # truss2D_RL.OUNoise.gen_noise per scalar (:41-48), all columns at once
                     for out, noises in ((g, ag.noise_geo), (t, ag.noise_topo)):
                         th_dt, mu, sg = self._noise_vectors(noises)
                         out.addcmul_(th_dt, mu - out).addcmul_(sg, torch.randn(out.shape, device=out.device, generator=self.gen))
@@ -916,7 +1079,7 @@ class BatchedMARL:
                 with torch.no_grad():
                     for ag_ in self.rl.agents:
                         actor_infer(self.lib, ag_.actor_model, [S[0][:1], self.A_n[0], S[2][:1], S[3][:1], S[4][:1], S[6][:1], S[7][:1]],
-                                    nbr=self.nbr, nbr_p=self.nbr_p, fused=self.actor_path == "fused",
+                                    nbr=self.nbr, nbr_p=self.nbr_p, fused=self.actor_path != "layers",   # (grouped: the same caches)
                                     precision=self.actor_precision)
                 snap =[[p.detach().clone() for p in n.parameters()] for n in nets]
                 osnap = [t.clone() for t in self.rl.critics_opt.state_tensors()]    # [] = no step taken yet (one optimiser for the three critics)

@@ -17,7 +17,16 @@ with a Pareto graph of 20 members (the train game) and 4096 pairs with 50 member
 
 times actor_infer(precision=...) instead (one child process): per shape (4096 and 14 336 pairs, P 20), actor path (layers, fused) and
 reduced precision T ("bf16x2", "bf16"), medians of 60 synchronised calls in alternating blocks  bf16x3, T, bf16x3 again,  and the
-largest deviation of T's action tensors from the bf16x3 ones."""
+largest deviation of T's action tensors from the bf16x3 ones.
+
+    python tools/actor_probe.py --grouped [OUT_DIR]     -> OUT_DIR/actor_grouped.json
+
+times the THREE-actor call of BatchedMARL._act (without the noise): three actor_infer(fused=True) calls against one
+marl.actors_infer call (truss_gcn_layer_group: every depth of the three actors' layers in one launch), two child processes as above.
+"grouped_time": medians of 60 synchronised calls in alternating blocks  fused, grouped, fused again,  and whether the outputs are
+bitwise equal; "grouped_launches": device kernels per call and their summed device time (torch.profiler), all kernels and the native
+ones.  Shapes: the small_roof widths at 512, 4096 and 14 336 pairs with P = 20 and 4096 pairs with P = 50, and the 256-node class at
+128 pairs."""
 import json
 import os
 import statistics
@@ -36,14 +45,28 @@ SHAPES = (          # (label, pairs, P)
 ROUNDS, BLOCK = 4, 15          # timed calls per path: ROUNDS alternating blocks of BLOCK
 
 
-def setup(B, P, dev):
+GROUP_SHAPES = (    # (label, pairs, P, num_x): what BatchedMARL._act evaluates, three actors on the same inputs
+    ("small_roof 512 pairs, P 20", 512, 20, 8),
+    ("small_roof 4096 pairs, P 20", 4096, 20, 8),
+    ("small_roof 14336 pairs, P 20", 14336, 20, 8),
+    ("small_roof 4096 pairs, P 50", 4096, 50, 8),
+    ("256 nodes, 128 pairs, P 20", 128, 20, 128),
+    # the classes of the mixed sweep (bench_configs.mixed_marl: 1024 / 512 / 256 / 128 envs) at a pass of 4 pairs per env
+    ("32 nodes, 4096 pairs, P 20", 4096, 20, 16),
+    ("64 nodes, 2048 pairs, P 20", 2048, 20, 32),
+    ("128 nodes, 1024 pairs, P 20", 1024, 20, 64),
+    ("256 nodes, 512 pairs, P 20", 512, 20, 128),
+)
+
+
+def setup(B, P, dev, num_x=8):
     import numpy as np
     import torch
     import truss_mi355 as tm
     from truss_mi355 import marl
     import truss2D_RL as RL
     torch.manual_seed(B + P)
-    topo = tm.TrussTopology.grid(8)
+    topo = tm.TrussTopology.grid(num_x)
     N, tab = topo.N, topo.neighbor_table()
     patt = np.zeros((N, N), bool)
     for i in range(N):
@@ -182,6 +205,90 @@ def child_launches():
     print(json.dumps(out))
 
 
+def three_actor_paths(lib, B, P, num_x, dev):
+    """what BatchedMARL._act does without the noise: the three actors on the same inputs, one after the other through
+    actor_infer(fused=True), or level by level through actors_infer"""
+    import torch
+    from truss_mi355 import marl
+    import truss2D_RL as RL
+    actor, ins, kw = setup(B, P, dev, num_x)
+    actors = [actor] + [RL.multimodes_actor(200, 2, 3).to(dev) for _ in range(2)]
+
+    def fused():
+        with torch.no_grad():
+            return [marl.actor_infer(lib, a, ins, fused=True, **kw) for a in actors]
+
+    def grouped():
+        with torch.no_grad():
+            return marl.actors_infer(lib, actors, ins, **kw)
+    return {"fused": fused, "grouped": grouped}
+
+
+def child_grouped_time():
+    import torch
+    import truss_mi355 as tm
+    dev = torch.device("cuda")
+    lib = tm.load()
+    out = {}
+    for label, B, P, num_x in GROUP_SHAPES:
+        fn = three_actor_paths(lib, B, P, num_x, dev)
+
+        def times(f, n):
+            ts = []
+            for _ in range(n):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                f()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e6)
+            return ts
+
+        for f in fn.values():
+            times(f, 10)
+        ts = {"fused": [], "grouped": [], "fused_again": []}
+        for _ in range(ROUNDS):                                        # alternating blocks: fused, grouped, fused, ...
+            for k in ts:
+                ts[k] += times(fn["grouped" if k == "grouped" else "fused"], BLOCK)
+        a, b = fn["fused"](), fn["grouped"]()
+        out[label] = {"call_us": {k: round(statistics.median(v), 1) for k, v in ts.items()}, "calls_per_median": ROUNDS * BLOCK,
+                      "outputs_equal": all(bool(torch.equal(x, y)) for p, q in zip(a, b) for x, y in zip(p, q))}
+        del fn, a, b
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
+def child_grouped_launches():
+    import torch
+    from torch.profiler import profile, ProfilerActivity
+    import truss_mi355 as tm
+    dev = torch.device("cuda")
+    lib = tm.load()
+    out = {}
+    for label, B, P, num_x in GROUP_SHAPES:
+        for path, f in three_actor_paths(lib, B, P, num_x, dev).items():
+            for _ in range(3):
+                f()
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+                f()
+                torch.cuda.synchronize()
+            kern = {}
+            for e in prof.key_averages():
+                if e.device_type == torch.autograd.DeviceType.CUDA:
+                    us = getattr(e, "device_time_total", None)
+                    us = e.cuda_time_total if us is None else us
+                    c, t = kern.get(e.key, (0, 0.0))
+                    kern[e.key] = (c + e.count, t + us)
+            native = lambda k: "truss_" in k
+            out[f"{label} path={path}"] = {
+                "launches": sum(c for c, _ in kern.values()), "device_us": round(sum(t for _, t in kern.values()), 1),
+                "native_launches": sum(c for k, (c, _) in kern.items() if native(k)),
+                "native_device_us": round(sum(t for k, (_, t) in kern.items() if native(k)), 1),
+                "kernels": {k[:110]: {"count": c, "device_us": round(t, 1)} for k, (c, t) in sorted(kern.items())}}
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main():
     out_dir = os.path.abspath(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "build", "actor_probe"))
     os.makedirs(out_dir, exist_ok=True)
@@ -189,9 +296,14 @@ def main():
     env = dict(os.environ, TMPDIR="/tmp")
     result = {}
     precision = "--precision" in sys.argv[1:2]
-    if precision:
+    grouped = "--grouped" in sys.argv[1:2]
+    if precision or grouped:
         out_dir = os.path.abspath(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "build", "actor_probe"))
-    for step, limit in ((("precision", "300"),) if precision else (("time", "300"), ("launches", "180"))):
+        os.makedirs(out_dir, exist_ok=True)
+    steps = (("precision", "300"),) if precision else (("grouped_time", "300"), ("grouped_launches", "180")) if grouped else \
+        (("time", "300"), ("launches", "180"))
+    name = "actor_precision.json" if precision else "actor_grouped.json" if grouped else "actor_probe.json"
+    for step, limit in steps:
         p = subprocess.run(["timeout", "-k", "10", limit, sys.executable, me, "--child", step], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True)
         with open(os.path.join(out_dir, step + ".err"), "w") as f:
@@ -200,13 +312,14 @@ def main():
             print(f"the {step} step failed with status {p.returncode}\n{p.stderr[-2000:]}", file=sys.stderr)
             sys.exit(1)
         result[step] = json.loads(p.stdout.strip().splitlines()[-1])
-        with open(os.path.join(out_dir, "actor_precision.json" if precision else "actor_probe.json"), "w") as f:
+        with open(os.path.join(out_dir, name), "w") as f:
             json.dump(result, f, indent=1)
     print(json.dumps(result, indent=1))
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--child":
-        {"time": child_time, "launches": child_launches, "precision": child_precision}[sys.argv[2]]()
+        {"time": child_time, "launches": child_launches, "precision": child_precision, "grouped_time": child_grouped_time,
+         "grouped_launches": child_grouped_launches}[sys.argv[2]]()
     else:
         main()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic: operators and device kernels of ONE batched game step (small_roof, 4096 envs) by section, torch.profiler.
-   tools/game_step_ops.py [train 0/1] [reward_path torch/hip] [archive_path torch/hip] [actor_precision] [actor_path layers/fused]"""
+   tools/game_step_ops.py [train 0/1] [reward_path torch/hip] [archive_path torch/hip] [actor_precision] [actor_path layers/fused/grouped]"""
 import contextlib, io, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "mop-truss-marl_amd"), ROOT]
@@ -52,8 +52,9 @@ with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
 ev = prof.key_averages()
 kern = [(e.count, e.device_time_total / 1e3, e.key) for e in ev if e.device_type == torch.autograd.DeviceType.CUDA]
 print("device kernels:", sum(c for c, _, _ in kern), " device time %.2f ms" % sum(t for _, t, _ in kern))
-print("  GCN layer kernels (truss_gcn_layer*):", sum(c for c, _, k in kern if "truss_gcn_layer" in k),
-      " device time %.3f ms" % sum(t for _, t, k in kern if "truss_gcn_layer" in k))
+gcn = ("truss_gcn_layer", "truss_gcn_group")                 # the layer kernels and the grouped launch of them (actor_path "grouped")
+print("  GCN layer kernels (truss_gcn_layer*, truss_gcn_group*):", sum(c for c, _, k in kern if any(g in k for g in gcn)),
+      " device time %.3f ms" % sum(t for _, t, k in kern if any(g in k for g in gcn)))
 big = ("truss_step_kernel", "truss_obs_kernel", "truss_rollout_kernel", "truss_gcn")       # the FEM / observation / GCN kernels
 print("  outside the GCN / FEM kernels:", sum(c for c, _, k in kern if not any(b in k for b in big)),
       " of them truss_front_kernel:", sum(c for c, _, k in kern if "truss_front_kernel" in k),
