@@ -368,6 +368,82 @@ typedef struct truss_archive_args {
 } truss_archive_args_t;
 int truss_archive_merge(const truss_archive_args_t *args, void *stream);
 
+/* ---- set-up of a chunk of (env, member) pairs of a game step, one launch for K pairs ------------------
+ * replaces: the block of indexing operators with which truss_mi355/marl.py starts every chunk of a game step (the prologue of
+ * master_DDPG_truss2D_MO.run() :211-260 per archive member, batched): the gathers of the step-start archive and the per-env
+ * constants, the copies into the parent and candidate env objects, truss2D_ENV.pareto_state_data (:19-38) padded to P nodes, and
+ * the symmetry coins of the design game.  Nothing is computed beyond one conversion, one division or one product per element.
+ *
+ * Pair k < K is (env idx[k], member ms[k]); idx and ms are int64 (what the framework's nonzero returns), idx may repeat an env any
+ * number of times and need not be sorted.  With b = idx[k], m = ms[k], n = clamp(n[b], 0, P):
+ *   par_x / par_target / par_params / par_y / par_sec   row k       = c_x[b], c_target[b], c_params[b], arch_y[b][m], arch_sec[b][m]
+ *   cand_x / cand_target / cand_params / cand_y / cand_sec  rows a K + k, a = 0..2 = the same five rows (agent-major)
+ *   p0 [K][P][4] = pts[b]     nn0 [K] = n[b] (as stored)     parent_obj [K][2] = pts[b][m][0:2]     ref [K][2] = ref_points[b]
+ *   x_p [rep K][P][4] float32, row i < n: [ (float)pts[b][i][0], (float)pts[b][i][1], i == m ? 1 : 0, frac ]
+ *                     (conversions round to nearest); rows i >= n: exact zeros.  frac = (float)n / (float)P, ONE float32 division
+ *                     -- or, with frac_tab, the caller's frac_tab[n]: a framework that divides a tensor by a host scalar as a
+ *                     product with the rounded reciprocal (two roundings: 49 / 50 comes out one ulp lower) is matched by handing
+ *                     over the table it computes, as with dtab
+ *   A_p [rep K][P][P] float32: dtab[deg_i] * dtab[deg_j] (ONE float32 product) for |i - j| <= 1 and i, j < n, else exact zero,
+ *                     deg_i = 1 + [i > 0] + [i + 1 < n]: the path over the n members with self loops, symmetrically normalised.
+ *                     dtab[d] is the caller's float32 value of d^-1/2 for d = 1, 2, 3 (dtab[0] is not read): the caller decides how
+ *                     that is rounded, so that A_p carries the bits of whatever host computation it stands in for
+ *   rows a K + k of x_p / A_p are equal for every a < rep (rep = 3: the candidates' next states see their parent's front)
+ *   coin [3 K] uint8 or NULL: coin[a K + k] = top bit of splitmix64(splitmix64(seed) ^ (env_ids[b] << 26 | game_step << 10 | m << 2 | a))
+ *                     in 64-bit wrap-around arithmetic
+ * Only rows [0, K) (3 K, rep K) of the outputs are written.  Two workgroups per pair (the design rows; everything else); plain
+ * vector loads and stores, 16 bytes where both the piece and the address allow it; no LDS, no atomics, every output word has one
+ * owner.  Device pointers; the library neither allocates nor synchronises (capturable in a hipGraph).
+ * idx[k] outside [0, n_envs) or ms[k] outside [0, P) is the caller's error and is not detected (that would need a synchronisation):
+ * both are clamped into range before they index anything, so such a pair reads some env's rows and writes its own rows only.
+ * TRUSS_EINVAL, naming the argument, with nothing launched or written: bad struct_size, n_pairs < 0, n_envs < 0 (< 1 with pairs),
+ * max_points outside 1..TRUSS_PAIR_MAXP, n_y / n_sec / n_param < 1, rep outside {1, 3}, flags != 0, 3 n_pairs (or n_envs max_points) times the
+ * widest row (max(P P, 8 P, n_y, n_sec, 2 n_param) words) above 2^31 - 1, a NULL pointer (coin and frac_tab may be NULL; env_ids may be
+ * NULL when coin is), a pointer not aligned to its element type, an output range that overlaps an input range or another output.
+ * n_pairs == 0: TRUSS_OK, no launch.  Optional symbol: a library of this ABI version may lack it. */
+#define TRUSS_PAIR_MAXP 256
+typedef struct truss_pair_args {
+  size_t struct_size;
+  int32_t n_pairs;           /* K */
+  int32_t n_envs;            /* B */
+  int32_t max_points;        /* P: rows of the archive per env */
+  int32_t n_y, n_sec;        /* N, E: words per design row of y / sec (x and target rows have n_y words too) */
+  int32_t n_param;           /* doubles per row of c_params (TRUSS_NPARAM) */
+  int32_t rep;               /* 1 or 3: copies of the Pareto graph */
+  uint32_t flags;            /* 0 */
+  int64_t seed;              /* the coin's seed */
+  int64_t game_step;         /* the coin's step field */
+  float dtab[4];             /* [0, 1^-1/2, 2^-1/2, 3^-1/2] as the caller rounds them */
+  const int64_t *idx;        /* [K] */
+  const int64_t *ms;         /* [K] */
+  const double *pts;         /* [B][P][4] */
+  const int32_t *n;          /* [B] */
+  const float *arch_y;       /* [B][P][n_y] */
+  const int32_t *arch_sec;   /* [B][P][n_sec] */
+  const float *c_x;          /* [B][n_y] */
+  const float *c_target;     /* [B][n_y] */
+  const double *c_params;    /* [B][n_param] */
+  const double *ref_points;  /* [B][2] */
+  const int64_t *env_ids;    /* [B]; may be NULL when coin is */
+  const float *frac_tab;     /* [P + 1] or NULL: column 3 of x_p for n = 0..P instead of (float)n / (float)P */
+  float *par_x, *par_target; /* [K][n_y] */
+  double *par_params;        /* [K][n_param] */
+  float *par_y;              /* [K][n_y] */
+  int32_t *par_sec;          /* [K][n_sec] */
+  float *cand_x, *cand_target; /* [3 K][n_y] */
+  double *cand_params;       /* [3 K][n_param] */
+  float *cand_y;             /* [3 K][n_y] */
+  int32_t *cand_sec;         /* [3 K][n_sec] */
+  double *p0;                /* [K][P][4] */
+  int32_t *nn0;              /* [K] */
+  double *parent_obj;        /* [K][2] */
+  double *ref;               /* [K][2] */
+  float *x_p;                /* [rep K][P][4] */
+  float *A_p;                /* [rep K][P][P] */
+  uint8_t *coin;             /* [3 K] or NULL */
+} truss_pair_args_t;
+int truss_pair_setup(const truss_pair_args_t *args, void *stream);
+
 /* ---- GCN neighbourhood aggregation for the actors' inference in batched rollouts -----------------
  * replaces (inference only): the `A @ (X W) + b` + activation half of spektral GCNConv as used by
  * truss2D_RL.multimodes_actor (truss2D_RL.py:49-120): out[b][i][c] = act(sum_j A[b][i][j] H[b][j][c] + bias[c])

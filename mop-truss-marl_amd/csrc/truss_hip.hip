@@ -8,7 +8,8 @@
 //
 // This file holds the step, rollout and observation kernels and their launch glue only.  Every other kernel family has a
 // header of its own, included at the end: truss_gcn.h, truss_gcn_level.h, truss_gcn_level_bwd.h, truss_replay.h, truss_front.h
-// (Pareto front + hypervolume), truss_reward.h (the difference reward), truss_archive.h (the archive update) and truss_gcn_aggregate.h.
+// (Pareto front + hypervolume), truss_reward.h (the difference reward), truss_archive.h (the archive update),
+// truss_pairs.h (the set-up of a chunk of pairs) and truss_gcn_aggregate.h.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -491,4 +492,5 @@ extern "C" int truss_debug_stamps(unsigned long long *out16) {
 #include "truss_front.h"
 #include "truss_reward.h"
 #include "truss_archive.h"
+#include "truss_pairs.h"
 #include "truss_gcn_aggregate.h"

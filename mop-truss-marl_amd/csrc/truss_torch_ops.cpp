@@ -41,7 +41,8 @@
   X(archive_merge, truss_archive_merge, false)                   \
   X(gcn_layer_fused, truss_gcn_layer_fused, false)               \
   X(gcn_layer_terms, truss_gcn_layer_terms, false)               \
-  X(gcn_layer_group, truss_gcn_layer_group, false)
+  X(gcn_layer_group, truss_gcn_layer_group, false)               \
+  X(pair_setup, truss_pair_setup, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -654,6 +655,94 @@ void archive_merge(int64_t lib, int64_t stream, int64_t max_front, int64_t n_slo
   check_rc(b, b.archive_merge(&a, (void *)stream), "truss_archive_merge");
 }
 
+// the set-up of K (env, member) pairs of a game step in one launch: design rows of the parents and (three times) the candidates,
+// the step-start archive, the Pareto-graph observation (rep copies) and the design game's coins == truss_pair_setup.
+// K = idx.numel(); the outputs may hold more rows than the call writes (the env objects' resident buffers)
+void pair_setup(int64_t lib, int64_t stream, int64_t rep, int64_t seed, int64_t game_step, at::ArrayRef<double> dtab, const at::Tensor &idx,
+                const at::Tensor &ms, const at::Tensor &pts, const at::Tensor &n, const at::Tensor &arch_y, const at::Tensor &arch_sec,
+                const at::Tensor &c_x, const at::Tensor &c_target, const at::Tensor &c_params, const at::Tensor &ref_points, const OT &env_ids,
+                const OT &frac_tab, const at::Tensor &par_x, const at::Tensor &par_target, const at::Tensor &par_params, const at::Tensor &par_y,
+                const at::Tensor &par_sec, const at::Tensor &cand_x, const at::Tensor &cand_target, const at::Tensor &cand_params,
+                const at::Tensor &cand_y, const at::Tensor &cand_sec, const at::Tensor &p0, const at::Tensor &nn0, const at::Tensor &parent_obj,
+                const at::Tensor &ref, const at::Tensor &x_p, const at::Tensor &A_p, const OT &coin) {
+  const Backend &b = backend(lib);
+  need(b.pair_setup, "truss_pair_setup");
+  TORCH_CHECK(pts.dim() == 3 && pts.size(2) == 4, "truss_mi355: pair_setup: pts must be [B, P, 4]");
+  const int64_t B = pts.size(0), P = pts.size(1);
+  TORCH_CHECK(idx.dim() == 1 && ms.dim() == 1 && ms.size(0) == idx.size(0), "truss_mi355: pair_setup: idx / ms must be [K]");
+  const int64_t K = idx.size(0);
+  TORCH_CHECK(arch_y.dim() == 3 && arch_y.size(0) == B && arch_y.size(1) == P, "truss_mi355: pair_setup: arch_y must be [B, P, N]");
+  TORCH_CHECK(arch_sec.dim() == 3 && arch_sec.size(0) == B && arch_sec.size(1) == P, "truss_mi355: pair_setup: arch_sec must be [B, P, E]");
+  const int64_t N = arch_y.size(2), E = arch_sec.size(2);
+  TORCH_CHECK(c_params.dim() == 2 && c_params.size(0) == B, "truss_mi355: pair_setup: c_params must be [B, NPARAM]");
+  const int64_t NP = c_params.size(1);
+  auto rows_of = [](const at::Tensor &t, int64_t rows, int64_t width) { return t.dim() == 2 && t.size(0) == rows && t.size(1) == width; };
+  TORCH_CHECK(n.dim() == 1 && n.size(0) == B && rows_of(c_x, B, N) && rows_of(c_target, B, N) && rows_of(ref_points, B, 2),
+              "truss_mi355: pair_setup: n [B], c_x / c_target [B, N], ref_points [B, 2]");
+  TORCH_CHECK(!present(env_ids) || (env_ids->dim() == 1 && env_ids->size(0) == B), "truss_mi355: pair_setup: env_ids must be [B]");
+  TORCH_CHECK(!present(frac_tab) || (frac_tab->dim() == 1 && frac_tab->size(0) == P + 1), "truss_mi355: pair_setup: frac_tab must be [P + 1]");
+  TORCH_CHECK(rep == 1 || rep == 3, "truss_mi355: pair_setup: rep must be 1 or 3");
+  TORCH_CHECK(dtab.size() == 4, "truss_mi355: pair_setup: dtab must hold 4 values");
+  TORCH_CHECK(K <= INT32_MAX / 3 && B <= INT32_MAX && P <= INT32_MAX && N <= INT32_MAX && E <= INT32_MAX && NP <= INT32_MAX,
+              "truss_mi355: pair_setup: a size does not fit 32 bits");
+  // outputs: at least the rows the call writes, with the row shape of the input they copy
+  auto out_rows = [](const at::Tensor &t, int64_t rows, at::IntArrayRef row, const char *name) {
+    TORCH_CHECK(t.dim() == (int64_t)row.size() + 1 && t.size(0) >= rows && t.sizes().slice(1) == row, "truss_mi355: pair_setup: ", name, " must be [>= ",
+                rows, ", ...] with rows of shape ", row);
+  };
+  out_rows(par_x, K, {N}, "par_x"); out_rows(par_target, K, {N}, "par_target"); out_rows(par_params, K, {NP}, "par_params");
+  out_rows(par_y, K, {N}, "par_y"); out_rows(par_sec, K, {E}, "par_sec");
+  out_rows(cand_x, 3 * K, {N}, "cand_x"); out_rows(cand_target, 3 * K, {N}, "cand_target"); out_rows(cand_params, 3 * K, {NP}, "cand_params");
+  out_rows(cand_y, 3 * K, {N}, "cand_y"); out_rows(cand_sec, 3 * K, {E}, "cand_sec");
+  out_rows(p0, K, {P, 4}, "p0"); out_rows(nn0, K, {}, "nn0"); out_rows(parent_obj, K, {2}, "parent_obj"); out_rows(ref, K, {2}, "ref");
+  out_rows(x_p, rep * K, {P, 4}, "x_p"); out_rows(A_p, rep * K, {P, P}, "A_p");
+  if (present(coin)) out_rows(*coin, 3 * K, {}, "coin");
+  const auto f32 = at::kFloat, f64 = at::kDouble, i32 = at::kInt, i64 = at::kLong;
+  truss_pair_args_t a{};
+  a.struct_size = sizeof(truss_pair_args_t);
+  a.n_pairs = (int32_t)K;
+  a.n_envs = (int32_t)B;
+  a.max_points = (int32_t)P;
+  a.n_y = (int32_t)N;
+  a.n_sec = (int32_t)E;
+  a.n_param = (int32_t)NP;
+  a.rep = (int32_t)rep;
+  a.seed = seed;
+  a.game_step = game_step;
+  for (int i = 0; i < 4; ++i) a.dtab[i] = (float)dtab[i];
+  a.idx = ptr<const int64_t>(b, idx, i64, "idx");
+  a.ms = ptr<const int64_t>(b, ms, i64, "ms");
+  a.pts = ptr<const double>(b, pts, f64, "pts");
+  a.n = ptr<const int32_t>(b, n, i32, "n");
+  a.arch_y = ptr<const float>(b, arch_y, f32, "arch_y");
+  a.arch_sec = ptr<const int32_t>(b, arch_sec, i32, "arch_sec");
+  a.c_x = ptr<const float>(b, c_x, f32, "c_x");
+  a.c_target = ptr<const float>(b, c_target, f32, "c_target");
+  a.c_params = ptr<const double>(b, c_params, f64, "c_params");
+  a.ref_points = ptr<const double>(b, ref_points, f64, "ref_points");
+  a.env_ids = ptr<const int64_t>(b, env_ids, i64, "env_ids");
+  a.frac_tab = ptr<const float>(b, frac_tab, f32, "frac_tab");
+  a.par_x = ptr<float>(b, par_x, f32, "par_x");
+  a.par_target = ptr<float>(b, par_target, f32, "par_target");
+  a.par_params = ptr<double>(b, par_params, f64, "par_params");
+  a.par_y = ptr<float>(b, par_y, f32, "par_y");
+  a.par_sec = ptr<int32_t>(b, par_sec, i32, "par_sec");
+  a.cand_x = ptr<float>(b, cand_x, f32, "cand_x");
+  a.cand_target = ptr<float>(b, cand_target, f32, "cand_target");
+  a.cand_params = ptr<double>(b, cand_params, f64, "cand_params");
+  a.cand_y = ptr<float>(b, cand_y, f32, "cand_y");
+  a.cand_sec = ptr<int32_t>(b, cand_sec, i32, "cand_sec");
+  a.p0 = ptr<double>(b, p0, f64, "p0");
+  a.nn0 = ptr<int32_t>(b, nn0, i32, "nn0");
+  a.parent_obj = ptr<double>(b, parent_obj, f64, "parent_obj");
+  a.ref = ptr<double>(b, ref, f64, "ref");
+  a.x_p = ptr<float>(b, x_p, f32, "x_p");
+  a.A_p = ptr<float>(b, A_p, f32, "A_p");
+  a.coin = ptr<uint8_t>(b, coin, at::kByte, "coin");
+  if (K == 0) return;
+  check_rc(b, b.pair_setup(&a, (void *)stream), "truss_pair_setup");
+}
+
 // every operator on meta tensors (tracing): nothing to compute, the schema says what is mutated
 void noop_boxed(const c10::OperatorHandle &op, torch::jit::Stack *s) { torch::jit::drop(*s, op.schema().arguments().size()); }
 
@@ -735,6 +824,11 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("gcn_layer_group(int lib, int stream, Tensor[] x, Tensor[] adj, Tensor?[] nbr, Tensor[] w, Tensor?[] bias, Tensor(a!)?[] out, int[] act, "
         "bool[] accumulate, Tensor[] w_split, int steps_per_chain, int kind, Tensor?[] w2, Tensor?[] bias2, Tensor?[] adj2, Tensor?[] nbr2, "
         "int[] act2, Tensor(b!)?[] out2, Tensor(c!)?[] pool, int terms) -> ()");
+  m.def("pair_setup(int lib, int stream, int rep, int seed, int game_step, float[] dtab, Tensor idx, Tensor ms, Tensor pts, Tensor n, Tensor arch_y, "
+        "Tensor arch_sec, Tensor c_x, Tensor c_target, Tensor c_params, Tensor ref_points, Tensor? env_ids, Tensor? frac_tab, Tensor(a!) par_x, Tensor(b!) par_target, "
+        "Tensor(c!) par_params, Tensor(d!) par_y, Tensor(e!) par_sec, Tensor(f!) cand_x, Tensor(g!) cand_target, Tensor(h!) cand_params, "
+        "Tensor(i!) cand_y, Tensor(j!) cand_sec, Tensor(k!) p0, Tensor(l!) nn0, Tensor(m!) parent_obj, Tensor(n!) ref, Tensor(o!) x_p, "
+        "Tensor(p!) A_p, Tensor(q!)? coin) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

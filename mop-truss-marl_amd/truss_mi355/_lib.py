@@ -83,6 +83,21 @@ class ArchiveArgs(C.Structure):
 ARCHIVE_MAXROWS = 256     # truss_archive_merge: P archive rows + C candidate slots on one 256-thread workgroup
 
 
+class PairArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_size_t), ("n_pairs", C.c_int32), ("n_envs", C.c_int32), ("max_points", C.c_int32), ("n_y", C.c_int32),
+        ("n_sec", C.c_int32), ("n_param", C.c_int32), ("rep", C.c_int32), ("flags", C.c_uint32), ("seed", C.c_int64),
+        ("game_step", C.c_int64), ("dtab", C.c_float * 4), ("idx", _vp), ("ms", _vp), ("pts", _vp), ("n", _vp), ("arch_y", _vp),
+        ("arch_sec", _vp), ("c_x", _vp), ("c_target", _vp), ("c_params", _vp), ("ref_points", _vp), ("env_ids", _vp), ("frac_tab", _vp), ("par_x", _vp),
+        ("par_target", _vp), ("par_params", _vp), ("par_y", _vp), ("par_sec", _vp), ("cand_x", _vp), ("cand_target", _vp),
+        ("cand_params", _vp), ("cand_y", _vp), ("cand_sec", _vp), ("p0", _vp), ("nn0", _vp), ("parent_obj", _vp), ("ref", _vp),
+        ("x_p", _vp), ("A_p", _vp), ("coin", _vp),
+    ]
+
+
+PAIR_MAXP = 256           # truss_pair_setup: rows of the archive per env
+
+
 _i32, _i64 = C.c_int32, C.c_int64
 _STRING_GETTERS = ("truss_last_error", "truss_backend")       # return const char *; every other entry returns int
 # THE table of the C ABI (with _LATER_ENTRIES below, which see): (symbol, argtypes, optional).  A library may lack the optional entries (the CPU lane emulator does);
@@ -120,6 +135,7 @@ _LATER_ENTRIES = [
     ("truss_gcn_layer_fused", [_vp, _vp, _vp]),
     ("truss_gcn_layer_terms", [_vp, _vp, _i32, _vp]),
     ("truss_gcn_layer_group", [_vp, _vp, _i32, _i32, _i32, _vp]),
+    ("truss_pair_setup", [C.POINTER(PairArgs), _vp]),
 ]
 
 
@@ -156,6 +172,7 @@ class TrussLib:
         self.has_gcn_fused = "truss_gcn_layer_fused" in found                                # a GCN layer with its consumer in the epilogue
         self.has_gcn_terms = "truss_gcn_layer_terms" in found                                # the split-weight layer on one or two bf16 terms
         self.has_gcn_group = "truss_gcn_layer_group" in found                                # several split-weight layers in one launch
+        self.has_pair_setup = "truss_pair_setup" in found                                    # the fused set-up of a chunk of pairs
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")
         self.backend = d.truss_backend().decode()

@@ -818,6 +818,65 @@ def design_coins(seed, env_ids, game_step, members):
     return (_splitmix64(key ^ h0) < 0).to(torch.uint8)
 
 
+def pair_dtab(device):
+    """[0, 1^-1/2, 2^-1/2, 3^-1/2] as float32 values the way the framework rounds them on `device` (what `pareto_graph` gets from
+    `deg.pow(-0.5)` there): the table `pair_setup` takes, so that its A_p carries the bits of `pareto_graph`.  Synchronises once."""
+    return [0.0] + torch.tensor([1.0, 2.0, 3.0], dtype=torch.float32, device=device).pow(-0.5).tolist()
+
+
+def pair_frac_tab(max_front, device):
+    """float32 [P + 1]: column 3 of the Pareto-graph features for n = 0..P as `pareto_graph` computes it on `device` (`n.float() /
+    max_front`: on a GPU the framework multiplies by the rounded reciprocal of a host scalar, which is not always the correctly
+    rounded quotient -- 49 / 50 comes out one ulp lower): the table `pair_setup` takes so that its x_p carries those bits."""
+    return torch.arange(max_front + 1, dtype=torch.int32, device=device).float() / max_front
+
+
+_PAIR_ROWS = (("x", "c_x"), ("target", "c_target"), ("params", "c_params"), ("y", "arch_y"), ("sec", "arch_sec"))
+
+
+def pair_setup(lib, idx, ms, pts, n, arch_y, arch_sec, c_x, c_target, c_params, ref_points, *, rep=3, dtab=None, frac_tab=None,
+               coins=None, par=None, cand=None, out=None, stream=None):
+    """The set-up of K (env, member) pairs of a game step as one `truss_pair_setup` launch (include/truss_mi355.h, csrc/truss_pairs.h).
+
+    idx, ms [K] int64 (pair k = env idx[k], member ms[k]; envs may repeat)
+    pts [B,P,4] float64, n [B] int32, arch_y [B,P,N] float32, arch_sec [B,P,E] int32          the step-start archive
+    c_x, c_target [B,N] float32, c_params [B,NPARAM] float64, ref_points [B,2] float64        per-env constants
+    rep     1 or 3: copies of the Pareto graph (3: the candidates' next states, agent-major)
+    dtab    the four float32 values [0, 1, 2, 3]^-1/2 (default: `pair_dtab(device)`, which synchronises -- callers in a loop keep it)
+    frac_tab  None: column 3 of x_p is float(n) / float(P), one float32 division; or float32 [P + 1] with the value for every n
+              (`pair_frac_tab(P, device)`: what the framework computes there)
+    coins   None, or (seed, env_ids [B] int64, game_step): also the design game's coins (`design_coins`, agent-major)
+    par / cand   dicts x, target, params, y, sec of tensors with at least K / 3 K rows to write the design rows into (the env
+                 objects' resident buffers; rows behind stay as they are); None: new tensors
+    out     dict of preallocated p0, nn0, parent_obj, ref, x_p, A_p, coin to write into instead of new tensors
+    Returns dict(par, cand (the dicts), p0 [K,P,4], nn0 [K] int32, parent_obj [K,2], ref [K,2], x_p [rep K,P,4], A_p [rep K,P,P],
+    coin [3 K] uint8 or None).  No output may overlap an input."""
+    lib = lib or _lib.load()
+    if not lib.has_pair_setup:
+        raise _lib.TrussError(f"{lib.path} has no truss_pair_setup (the fused set-up of a chunk of pairs)")
+    if rep not in (1, 3):
+        raise ValueError(f"rep must be 1 or 3, got {rep!r}")
+    K, (B, P), dev = int(idx.shape[0]), pts.shape[:2], pts.device
+    src = dict(c_x=c_x, c_target=c_target, c_params=c_params, arch_y=arch_y, arch_sec=arch_sec)
+    rows = lambda given, mult: {k: (given[k] if given is not None else torch.empty((mult * K, src[s].shape[-1]), dtype=src[s].dtype, device=dev))
+                                for k, s in _PAIR_ROWS}
+    par, cand = rows(par, 1), rows(cand, 3)
+    out = dict(out or {})
+    new = lambda key, shape, dt: out[key] if key in out else torch.empty(shape, dtype=dt, device=dev)
+    res = dict(par=par, cand=cand, p0=new("p0", (K, P, 4), torch.float64), nn0=new("nn0", (K,), torch.int32),
+               parent_obj=new("parent_obj", (K, 2), torch.float64), ref=new("ref", (K, 2), torch.float64),
+               x_p=new("x_p", (rep * K, P, 4), torch.float32), A_p=new("A_p", (rep * K, P, P), torch.float32),
+               coin=new("coin", (3 * K,), torch.uint8) if coins is not None else None)
+    seed, env_ids, game_step = coins if coins is not None else (0, None, 0)
+    from . import ops
+    stream_i = ops.stream_of(dev) if stream is None else int(getattr(stream, "value", stream) or 0)
+    ops.call(ops.namespace().pair_setup, ops.bind(lib), stream_i, int(rep), int(seed), int(game_step), list(dtab) if dtab is not None else pair_dtab(dev),
+             idx, ms, pts, n, arch_y, arch_sec, c_x, c_target, c_params, ref_points, env_ids, frac_tab,
+             par["x"], par["target"], par["params"], par["y"], par["sec"], cand["x"], cand["target"], cand["params"], cand["y"], cand["sec"],
+             res["p0"], res["nn0"], res["parent_obj"], res["ref"], res["x_p"], res["A_p"], res["coin"])
+    return res
+
+
 class BatchedMARL:
     """game: "train" (the train copy: MAX_FRONT 20, no coin, culls of at most 64 rows, D1) or "test" (the design game of the
     test copies, see the module docstring: needs a topology built with `symmetry=`; MAX_FRONT 50 unless max_front says
@@ -827,8 +886,13 @@ class BatchedMARL:
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
                  pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None,
                  level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None,
-                 archive_path: str | None = None, actor_path: str | None = None, actor_precision: str | None = None):
-        """actor_precision: the product of the actors' hidden layers in the ROLLOUT (`actor_infer(precision=...)`): "bf16x3" (float32
+                 archive_path: str | None = None, actor_path: str | None = None, actor_precision: str | None = None,
+                 pair_path: str | None = None):
+        """pair_path: how a game step sets up a chunk of (env, member) pairs -- "torch" (gathers of the step-start archive, copies into the
+        env objects, `pareto_graph`, `design_coins`: framework operators, the default) or "hip" (one `truss_pair_setup` launch per chunk;
+        needs a library with that entry); None: "hip" if the environment has TRUSS_PAIRS=hip, else "torch".  Both play the same game,
+        bit for bit.
+        actor_precision: the product of the actors' hidden layers in the ROLLOUT (`actor_infer(precision=...)`): "bf16x3" (float32
         accuracy, the default), "f32", or the reduced "bf16x2" / "bf16" (two terms / one term of the bf16 split, truncated: errors of
         up to 2^-13 / 2^-6 of a layer's magnitude, every product biased towards zero; need a library with `truss_gcn_layer_terms`);
         None: the environment's TRUSS_ACTOR_PRECISION, else "bf16x3".  Composes with actor_path; the update is not affected (it
@@ -910,6 +974,16 @@ class BatchedMARL:
                 raise ValueError(f"archive_path='hip': max_front {self.P} + {3 * self.Gm} candidate slots exceed the "
                                  f"{_lib.ARCHIVE_MAXROWS} rows of truss_archive_merge")
         self.archive_path = archive_path
+        if pair_path is None:
+            pair_path = "hip" if os.environ.get("TRUSS_PAIRS", "torch") == "hip" else "torch"
+        if pair_path not in ("torch", "hip"):
+            raise ValueError(f"pair_path must be 'torch' or 'hip', got {pair_path!r}")
+        if pair_path == "hip":
+            if not self.lib.has_pair_setup:
+                raise ValueError(f"pair_path='hip': {self.lib.path} has no truss_pair_setup")
+            if self.P > _lib.PAIR_MAXP:
+                raise ValueError(f"pair_path='hip': max_front {self.P} exceeds the {_lib.PAIR_MAXP} rows of truss_pair_setup")
+        self.pair_path = pair_path
         if actor_path is None:
             actor_path = os.environ.get("TRUSS_ACTOR", "layers")
             actor_path = actor_path if actor_path in ("fused", "grouped") else "layers"
@@ -927,6 +1001,8 @@ class BatchedMARL:
             raise ValueError(f"actor_precision={actor_precision!r}: {self.lib.path} has no truss_gcn_layer_terms")
         self.actor_precision = actor_precision
         self._arch_spare = None       # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
+        self._pair_dtab = self._pair_frac = None   # pair_path="hip": deg^-1/2 and n / P as the framework rounds them on this device
+        #                                             (pair_dtab, pair_frac_tab; made at the first step)
         if self.device.type == "cuda":
             import truss2D_RL
             truss2D_RL.set_level_backward(_level_backward_hook(self.lib) if level_backward == "hip" else None, "cuda")
@@ -1177,34 +1253,54 @@ class BatchedMARL:
                 tk = self._tick("other", tk)
                 idx, ms = pb_all[c0:c0 + self.cap], pm_all[c0:c0 + self.cap]
                 K = int(idx.numel())
-                ark = torch.arange(K, device=dev)
-                p0, nn0 = pts0[idx].contiguous(), n0[idx].contiguous()
-                py, ps = y0[idx, ms], sec0[idx, ms]
-                cx, ct, cp = self.c_x[idx], self.c_target[idx], self.c_params[idx]
-                # parents: the members of the step-start archive (:211-221)
                 eP, eC = self.envP, self.envC
-                eP.x[:K], eP.target[:K], eP.env_params[:K] = cx, ct, cp
-                eP.y[:K], eP.sec[:K] = py, ps
-                S = self._obs(eP, p0, nn0, ms, k=K, o=eP.analyze(n_active=K, obs=True))   # analysis + observations: one launch
+                hip_pairs = self.pair_path == "hip"
+                if hip_pairs:
+                    # one launch: the design rows of the parents and of their candidates straight into the env objects' buffers, the
+                    # step-start archive of every pair, the Pareto graph (three times over for the next states) and the coins
+                    if self._pair_dtab is None:
+                        self._pair_dtab, self._pair_frac = pair_dtab(dev), pair_frac_tab(P, dev)
+                    env_rows = lambda e: dict(x=e.x, target=e.target, params=e.env_params, y=e.y, sec=e.sec)
+                    pq = pair_setup(self.lib, idx, ms, pts0, n0, y0, sec0, self.c_x, self.c_target, self.c_params, self.ref_points,
+                                    rep=1 if test else 3, dtab=self._pair_dtab, frac_tab=self._pair_frac, par=env_rows(eP), cand=env_rows(eC),
+                                    coins=(self.seed, self.env_ids, self.game_step) if test else None)
+                    p0, nn0 = pq["p0"], pq["nn0"]
+                    ark = torch.arange(K, device=dev) if self.archive_path == "hip" and not test else None   # (the merge's table of rows)
+                    S = self._obs(eP, p0, nn0, ms, k=K, o=eP.analyze(n_active=K, obs=True), graph=(pq["x_p"][:K], pq["A_p"][:K]))
+                else:
+                    ark = torch.arange(K, device=dev)
+                    p0, nn0 = pts0[idx].contiguous(), n0[idx].contiguous()
+                    py, ps = y0[idx, ms], sec0[idx, ms]
+                    cx, ct, cp = self.c_x[idx], self.c_target[idx], self.c_params[idx]
+                    # parents: the members of the step-start archive (:211-221)
+                    eP.x[:K], eP.target[:K], eP.env_params[:K] = cx, ct, cp
+                    eP.y[:K], eP.sec[:K] = py, ps
+                    S = self._obs(eP, p0, nn0, ms, k=K, o=eP.analyze(n_active=K, obs=True))   # analysis + observations: one launch
                 tk = self._tick("parent analysis + obs", tk)
                 geo, topo = self._act(S, explore)
                 tk = self._tick("actors", tk)
                 # the three agents modify the SAME parent (:249-260): one launch over 3 K envs, agent-major
-                eC.x[:3 * K], eC.target[:3 * K], eC.env_params[:3 * K] = cx.repeat(3, 1), ct.repeat(3, 1), cp.repeat(3, 1)
-                eC.y[:3 * K], eC.sec[:3 * K] = py.repeat(3, 1), ps.repeat(3, 1)
+                if not hip_pairs:
+                    eC.x[:3 * K], eC.target[:3 * K], eC.env_params[:3 * K] = cx.repeat(3, 1), ct.repeat(3, 1), cp.repeat(3, 1)
+                    eC.y[:3 * K], eC.sec[:3 * K] = py.repeat(3, 1), ps.repeat(3, 1)
                 a_geo, a_topo = torch.cat(geo, 0).contiguous(), torch.cat(topo, 0).contiguous()
                 coin = None
                 if test:                                                                     # D6: agent-major like the candidates
-                    coin = design_coins(self.seed, self.env_ids[idx], self.game_step, ms).t().contiguous().view(-1)
+                    coin = pq["coin"] if hip_pairs else design_coins(self.seed, self.env_ids[idx], self.game_step, ms).t().contiguous().view(-1)
                 oC = eC.step(a_geo, a_topo, coin, clamp_inplace=True, n_active=3 * K, obs=not test)   # clamped actions go to the replay (:375);
                 self._steps_dev += 3 * K                                                     # step + next-state observations: one launch
-                NSall = None if test else self._obs(eC, p0, nn0, ms, rep=3, k=3 * K, o=oC, graph=(S["x_p"], S["A_p"]))
+                if test:
+                    NSall = None
+                elif hip_pairs:                                                              # the kernel wrote the three copies
+                    NSall = self._obs(eC, p0, nn0, ms, k=3 * K, o=oC, graph=(pq["x_p"], pq["A_p"]))
+                else:
+                    NSall = self._obs(eC, p0, nn0, ms, rep=3, k=3 * K, o=oC, graph=(S["x_p"], S["A_p"]))
                 tk = self._tick("candidate step + obs", tk)
                 points = eC.point[:3 * K].view(3, K, 4).permute(1, 0, 2).double().contiguous()
                 cand_y = eC.y[:3 * K].view(3, K, -1).permute(1, 0, 2)
                 cand_sec = eC.sec[:3 * K].view(3, K, -1).permute(1, 0, 2)
-                R, G_U, _, _ = RW.difference_reward(p0, nn0, p0, nn0, p0[ark, ms, :2].contiguous(), points, self.ref_points[idx].contiguous(),
-                                                    nn0, max_front=P, lib=self.lib, path=self.reward_path)
+                parent_obj, ref = (pq["parent_obj"], pq["ref"]) if hip_pairs else (p0[ark, ms, :2].contiguous(), self.ref_points[idx].contiguous())
+                R, G_U, _, _ = RW.difference_reward(p0, nn0, p0, nn0, parent_obj, points, ref, nn0, max_front=P, lib=self.lib, path=self.reward_path)
                 rsum.index_add_(0, idx, R)
                 tk = self._tick("reward", tk)
                 ok = (points[:, :, 2:4] <= 1).all(dim=2)                                      # archive candidates (:372)

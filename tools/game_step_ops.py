@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: operators and device kernels of ONE batched game step (small_roof, 4096 envs) by section, torch.profiler.
-   tools/game_step_ops.py [train 0/1] [reward_path torch/hip] [archive_path torch/hip] [actor_precision] [actor_path layers/fused/grouped]"""
+   tools/game_step_ops.py [train 0/1] [reward_path torch/hip] [archive_path torch/hip] [actor_precision] [actor_path layers/fused/grouped]
+                           [pair_path torch/hip]"""
 import contextlib, io, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "mop-truss-marl_amd"), ROOT]
@@ -16,10 +17,12 @@ reward_path = sys.argv[2] if len(sys.argv) > 2 else "torch"
 archive_path = sys.argv[3] if len(sys.argv) > 3 else "torch"
 actor_precision = sys.argv[4] if len(sys.argv) > 4 else "bf16x3"
 actor_path = sys.argv[5] if len(sys.argv) > 5 else "layers"
+pair_path = sys.argv[6] if len(sys.argv) > 6 else "torch"
 nx, B = 8, 4096
 topo = tm.TrussTopology.grid(nx)
 eng = marl.BatchedMARL(topo, B, BC._maddpg("cuda"), max_front=20, device="cuda", replay_capacity=32768, batch_size=32, tune_update_gemms=False,
-                       reward_path=reward_path, archive_path=archive_path, actor_precision=actor_precision, actor_path=actor_path)
+                       reward_path=reward_path, archive_path=archive_path, actor_precision=actor_precision, actor_path=actor_path,
+                       pair_path=pair_path)
 x = np.tile(np.arange(nx) * 5.0, 2)
 tar = np.concatenate([np.zeros(nx), 2.0 + 2.0 * np.abs(np.linspace(-1, 1, nx))])
 y0 = np.concatenate([np.zeros(nx), np.full(nx, 8.0)]).astype(np.float32)
@@ -35,7 +38,7 @@ with q:
     for _ in range(4):
         eng.game_step_all(train=train)
 torch.cuda.synchronize()
-print(f"reward_path {reward_path}  archive_path {archive_path}  actor_precision {actor_precision}  actor_path {actor_path}  game step: {(time.perf_counter() - t0) / 4 * 1e3:.2f} ms wall")
+print(f"reward_path {reward_path}  archive_path {archive_path}  actor_precision {actor_precision}  actor_path {actor_path}  pair_path {pair_path}  game step: {(time.perf_counter() - t0) / 4 * 1e3:.2f} ms wall")
 sections = {}
 orig_tick = eng._tick
 
@@ -59,7 +62,8 @@ big = ("truss_step_kernel", "truss_obs_kernel", "truss_rollout_kernel", "truss_g
 print("  outside the GCN / FEM kernels:", sum(c for c, _, k in kern if not any(b in k for b in big)),
       " of them truss_front_kernel:", sum(c for c, _, k in kern if "truss_front_kernel" in k),
       " truss_reward_kernel:", sum(c for c, _, k in kern if "truss_reward_kernel" in k),
-      " truss_archive_kernel:", sum(c for c, _, k in kern if "truss_archive_kernel" in k))
+      " truss_archive_kernel:", sum(c for c, _, k in kern if "truss_archive_kernel" in k),
+      " truss_pair_kernel:", sum(c for c, _, k in kern if "truss_pair_kernel" in k))
 for c, t, k in sorted(kern, key=lambda r: -r[1])[:24]:
     print(f"  {c:5d}  {t:7.3f} ms  {k[:100]}")
 ops = [(e.count, e.self_cpu_time_total / 1e3, e.key) for e in ev if e.device_type == torch.autograd.DeviceType.CPU]
