@@ -24,7 +24,7 @@ import pytest
 import torch
 
 import truss_mi355 as tm
-from truss_mi355 import marl, ops, synthetic
+from truss_mi355 import gcn, marl, ops, synthetic
 import parity_common as pc
 import gcn_reference as G
 import master_DDPG_truss2D_MO as M
@@ -280,7 +280,7 @@ def test_fused_is_reproducible_and_stays_in_bounds():
         for with_out in (False, False, True):
             o2 = Guarded((B, N, c2), "cuda")
             o = Guarded((B, N, C), "cuda") if with_out else None
-            marl._gcn_layer_fused(lib, x, adj, w, b, "relu", nbr, precision, None, o.t if o else None, 1, w2, b2, adj2, nbr2, c["act2"], out2=o2.t)
+            gcn._gcn_layer_fused(lib, x, adj, w, b, "relu", nbr, precision, None, o.t if o else None, 1, w2, b2, adj2, nbr2, c["act2"], out2=o2.t)
             assert o2.intact() and not bool(torch.isnan(o2.t).any()), f"{name} {precision}"
             assert o is None or (o.intact() and not bool(torch.isnan(o.t).any()))
             res.append(o2.t)
@@ -296,7 +296,7 @@ def test_fused_is_reproducible_and_stays_in_bounds():
         for with_out in (False, False, True):
             p = Guarded((B, C), "cuda")
             o = Guarded((B, N, C), "cuda") if with_out else None
-            marl._gcn_layer_fused(lib, x, adj, w, b, "relu", nbr, precision, None, o.t if o else None, 2, pool=p.t)
+            gcn._gcn_layer_fused(lib, x, adj, w, b, "relu", nbr, precision, None, o.t if o else None, 2, pool=p.t)
             assert p.intact() and not bool(torch.isnan(p.t).any()), f"{name} {precision}"
             assert o is None or (o.intact() and not bool(torch.isnan(o.t).any()))
             res.append(p.t)
@@ -443,7 +443,7 @@ def test_actor_infer_fused_float64_hip(P, monkeypatch):
     calls = {"layer": 0, "head": 0, "pool": 0}
     for key, fn in (("layer", "gcn_layer"), ("head", "gcn_layer_head"), ("pool", "gcn_layer_pool")):
         orig = getattr(marl, fn)
-        monkeypatch.setattr(marl, fn, lambda *a, _o=orig, _k=key, **k: (calls.__setitem__(_k, calls[_k] + 1), _o(*a, **k))[1])
+        monkeypatch.setattr(gcn, fn, lambda *a, _o=orig, _k=key, **k: (calls.__setitem__(_k, calls[_k] + 1), _o(*a, **k))[1])
     with torch.no_grad():
         f32 = actor(mod_in)
         ref = copy.deepcopy(actor).double()([t.double() for t in mod_in])

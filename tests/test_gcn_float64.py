@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import truss_mi355 as tm
-from truss_mi355 import marl, ops
+from truss_mi355 import gcn, marl, ops
 import parity_common as pc
 import gcn_reference as G
 import truss2D_RL as RL
@@ -121,7 +121,7 @@ def _check_gcn_layer_envelope(lib, device, monkeypatch):
     rn = lambda *s: torch.randn(*s, device=device)
     splits = []
     orig = marl.split_weights
-    monkeypatch.setattr(marl, "split_weights", lambda *a, **k: splits.append(1) or orig(*a, **k))
+    monkeypatch.setattr(gcn, "split_weights", lambda *a, **k: splits.append(1) or orig(*a, **k))
     w, b = rn(200, 200) / 14.0, rn(200)
     ws = orig(lib, w)
     for terms, want in ((9, "bf16x3"), (10, "f32")):

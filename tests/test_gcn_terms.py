@@ -24,7 +24,7 @@ import pytest
 import torch
 
 import truss_mi355 as tm
-from truss_mi355 import marl, ops
+from truss_mi355 import gcn, marl, ops
 import parity_common as pc
 import gcn_reference as G
 import test_actor_fused as F
@@ -282,7 +282,7 @@ def test_terms_are_reproducible_stay_in_bounds_and_refuse_cleanly():
         res = []
         for _ in range(2):
             o2 = F.Guarded((x.shape[0], x.shape[1], w2.shape[0]), "cuda")
-            marl._gcn_layer_fused(lib, x, adj, w, b, "relu", nbr, PRECISION[T], None, None, 1, w2, b2, adj2, nbr2, c["act2"], out2=o2.t)
+            gcn._gcn_layer_fused(lib, x, adj, w, b, "relu", nbr, PRECISION[T], None, None, 1, w2, b2, adj2, nbr2, c["act2"], out2=o2.t)
             assert o2.intact() and not bool(torch.isnan(o2.t).any()), f"head {name} T {T}"
             res.append(o2.t)
         assert torch.equal(res[0], res[1])
@@ -291,7 +291,7 @@ def test_terms_are_reproducible_stay_in_bounds_and_refuse_cleanly():
     res = []
     for _ in range(2):
         p = F.Guarded((x.shape[0], w.shape[0]), "cuda")
-        marl._gcn_layer_fused(lib, x, adj, w, b, "relu", nbr, "bf16x2", None, None, 2, pool=p.t)
+        gcn._gcn_layer_fused(lib, x, adj, w, b, "relu", nbr, "bf16x2", None, None, 2, pool=p.t)
         assert p.intact() and not bool(torch.isnan(p.t).any())
         res.append(p.t)
     assert torch.equal(res[0], res[1])
@@ -436,7 +436,7 @@ def test_actor_infer_precision_hip(T, monkeypatch):
         out0 = out.clone() if accumulate else None
         got = orig["gcn_layer"](lib_, x, adj, w, bias, act, nbr_, out, accumulate, precision=precision, w_split=w_split)
         ref, mag = G.layer_ref(x, adj, w, bias, act, out0)
-        env = precision != "f32" and marl._bf16_envelope(x, w, nbr_)
+        env = precision != "f32" and gcn._bf16_envelope(x, w, nbr_)
         r = G.max_ratio(got, ref, mag)
         key = "hidden" if env else "f32"
         worst[key] = max(worst[key], r)
@@ -446,7 +446,7 @@ def test_actor_infer_precision_hip(T, monkeypatch):
     def head(lib_, x, adj, w, bias, act, w2, bias2, adj2, act2, nbr_=None, nbr2=None, precision="bf16x3", w_split=None, out=None):
         calls["head"] += 1
         got = orig["gcn_layer_head"](lib_, x, adj, w, bias, act, w2, bias2, adj2, act2, nbr_, nbr2, precision=precision, w_split=w_split, out=out)
-        assert act == "relu" and marl._bf16_envelope(x, w, nbr_)
+        assert act == "relu" and gcn._bf16_envelope(x, w, nbr_)
         ref, bound = _head_bound(x, adj, w, bias, w2, bias2, adj2, act2, tau_hidden)
         r = F._ratio(got, ref, bound)
         worst["head"] = max(worst["head"], r)
@@ -456,7 +456,7 @@ def test_actor_infer_precision_hip(T, monkeypatch):
     def pool(lib_, x, adj, w, bias, act, nbr_=None, precision="bf16x3", w_split=None, out=None):
         calls["pool"] += 1
         got = orig["gcn_layer_pool"](lib_, x, adj, w, bias, act, nbr_, precision=precision, w_split=w_split, out=out)
-        assert act == "relu" and marl._bf16_envelope(x, w, nbr_)
+        assert act == "relu" and gcn._bf16_envelope(x, w, nbr_)
         ref, bound = _pool_bound(x, adj, w, bias, tau_hidden)
         r = F._ratio(got, ref, bound)
         worst["pool"] = max(worst["pool"], r)
@@ -472,9 +472,9 @@ def test_actor_infer_precision_hip(T, monkeypatch):
             assert torch.equal(b, f)
         for b, f in zip(base_fused, marl.actor_infer(lib, actor, ins, nbr=nbr, nbr_p=nbr_p, fused=True, precision="bf16x3")):
             assert torch.equal(b, f)
-        monkeypatch.setattr(marl, "gcn_layer", layer)
-        monkeypatch.setattr(marl, "gcn_layer_head", head)
-        monkeypatch.setattr(marl, "gcn_layer_pool", pool)
+        monkeypatch.setattr(gcn, "gcn_layer", layer)
+        monkeypatch.setattr(gcn, "gcn_layer_head", head)
+        monkeypatch.setattr(gcn, "gcn_layer_pool", pool)
         for fused, want in ((False, {"layer": 13, "head": 0, "pool": 0}), (True, {"layer": 8, "head": 2, "pool": 1})):
             calls.update(layer=0, head=0, pool=0)
             got = marl.actor_infer(lib, actor, ins, nbr=nbr, nbr_p=nbr_p, fused=fused, precision=PRECISION[T])
