@@ -34,6 +34,9 @@
 #include <stdint.h>
 #include <math.h>
 
+#ifndef TB_OPAQUE
+#define TB_OPAQUE(x) (x)  // device: the value behind a barrier the optimiser does not see through
+#endif
 #ifndef TB_SCHED_FENCE
 #define TB_SCHED_FENCE()  // device: __builtin_amdgcn_sched_barrier(0); pins hand-placed prefetches
 #endif
@@ -1007,22 +1010,36 @@ struct StepLane {
     }
   }
 
-  // back substitution, distributed over the lanes of the team:
+  // back substitution, distributed over the lanes of the team, as column sweeps:
   //   x_k = (z_k - sum_m A[k+m,k] x_{k+m}) / d_k
-  // Row k of the factor (the posted pivot column k with the pivot d_k in it, and z_k) is needed by ONE dot product.  Each
-  // lane therefore loads only the rows it owns -- row kb + gs (+ WL s) of a block of W steps, one set of
-  // loads per block instead of one per step and lane -- evaluates every step's dot product with its own
-  // row (only the owner's result means anything), and the owner's x_k reaches the other lanes of the
-  // team through a DPP row broadcast: registers only, no LDS round trip in the chain of dependent
-  // solutions.  (All lanes reading every row was 5 ds_read_b128 per step and wave: the LDS, shared by the
-  // four waves of a CU, was the bottleneck of this phase.)
-  //  * the terms are accumulated oldest-x first in two partial sums: only one fma, one multiply and the
-  //    broadcast depend on the x_{k+1} the previous step has just produced;
-  //  * the rows of the next block are requested while the current block is being solved.
-  double bc[RPL][W], bz[RPL], bd[RPL];   // rows owned in the current block
+  // Row k of the factor (the posted pivot column k with the pivot d_k in it, and z_k) belongs to ONE solution.  Each lane
+  // therefore loads only the rows it owns -- row p = kb + o, o = gs + WL s, of a block of W steps, one set of loads per
+  // block -- and keeps ONE accumulator per owned row, ba[s] = z_p - (the terms of the rows solved so far).  Entry j of the
+  // row is the coefficient of row kb + j for j > o (same block) and of row kb + W + j for j < o (the block above); entry o
+  // is d_p: the residue layout makes every register index a compile-time constant.
+  //  * adoption of a block (backsub_rows_adopt): the rows of the block above are all solved and sit in xs[]; their terms
+  //    (j < o: a select on the coefficient, the register index is not lane-dependent) go into the accumulator oldest x
+  //    first, in two partial sums, so that only one fma waits for the x the last step has just produced.  In the top
+  //    block the rows that do not exist contribute nothing: xs starts at zero (solver_init);
+  //  * a step (backsub_step) is one multiply, ba * (1/d_p), meaningful in the owner lane; the owner's x_k reaches the
+  //    team through a DPP row broadcast (registers only) and every lane sweeps it into its accumulators with ONE fma per
+  //    owned row (backsub_share).  No mask: rows below k take their true term, rows at or above k have already
+  //    produced their solution and their accumulator is dead (whatever it collects, the next adoption overwrites it);
+  //  * the rows of the next block are requested while the current block is being solved, and the reciprocals of their
+  //    pivots are finished in the middle of the block (backsub_rows_rcp): no block starts with a reciprocal chain.
+  // (Every lane evaluating every step's whole dot product with its own row, of which only the owner's was used, was 22
+  // VALU instructions per step; the phase was bound by their issue, not by the chain of dependent solutions.)
+  double bc[RPL][W], bz[RPL], bd[RPL];   // rows owned in the current block; bd = 1/d_p
   double nc[RPL][W], nz[RPL], nd[RPL];   // ... in the next block (in flight); nd = the pivot d itself
+  double ni[RPL];                        // 1/nd, once the rows have landed
+  double ba[RPL];                        // accumulators of the rows owned in the current block
+  int bgs;                               // gs, as seen by the back substitution (backsub_begin)
   double bx;                             // this lane's candidate for x_k (valid in the owner lane)
   double myx[RPL] = {};                  // x of the rows this lane owns in the current block
+  // The lane masks of the back substitution (t < gs) are compared against a copy of gs that the optimiser cannot trace back:
+  // computed from gs itself they are hoisted to the top of the kernel and stay live through the factorisation, where the
+  // scalar registers are short (the EMIT kernel then spills a 16-register tuple and keeps a stack frame for it).
+  TRUSS_HD void backsub_begin() { bgs = TB_OPAQUE(gs); }
   TRUSS_HD void backsub_rows_fetch(const TopoDev &T, int kb) {
 #pragma unroll
     for (int s = 0; s < RPL; ++s) {
@@ -1039,32 +1056,70 @@ struct StepLane {
       nd[s] = Kt[pc * W + pc % W];   // the pivot d_p (a register array must not be indexed by the lane id)
     }
   }
+  // 1/d_p of the fetched rows: the same operations as in the factorisation, so the same bits; once per block and lane,
+  // inside the block before the one that uses it (the fence keeps the chain from moving up to the head of the block,
+  // where it would wait for the rows)
+  TRUSS_HD void backsub_rows_rcp() {
+    TB_SCHED_FENCE();
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) ni[s] = tb_rcp(nd[s]);
+  }
+  // adoption: the rows of the block above are all solved and sit in xs[]; their terms (j < o) go into the accumulator,
+  // oldest x first.  bu[] keeps the masked coefficients for backsub_rebuild (dead, and in no register, anywhere else).
+  double bu[RPL][W];
   TRUSS_HD void backsub_rows_adopt() {
 #pragma unroll
     for (int s = 0; s < RPL; ++s) {
 #pragma unroll
       for (int j = 0; j < W; ++j) bc[s][j] = nc[s][j];
       bz[s] = nz[s];
-      // 1/d_p of the owned row: the same operations as in the factorisation, so the same bits; once per block and lane
-      bd[s] = tb_rcp(nd[s]);
+      bd[s] = ni[s];
+      const int o = bgs + WL * s;
+#pragma unroll
+      for (int j = 0; j < W; ++j) bu[s][j] = (j < W - 1 && j < o) ? bc[s][j] : 0.0;    // j = W - 1 < o cannot hold
+      double a0 = bz[s], a1 = 0.0;
+#pragma unroll
+      for (int j = W - 2; j >= 1; --j) {
+        if (j & 1) a1 = fma(-bu[s][j], xs[j], a1);
+        else a0 = fma(-bu[s][j], xs[j], a0);
+      }
+      // j = 0: the newest solution of the block above, the only term the last step's broadcast is waited for
+      ba[s] = fma(-bu[s][0], xs[0], a0 + a1);
+    }
+  }
+  // after backsub_reload, in the block whose steps kk = c-1 .. 0 are still to run: xs[] is what the LDS holds (team B's own
+  // middle steps worked on rows that are not its own), so the accumulators of the rows still to solve (o < c) are built
+  // again from it: the rows solved in this block (j >= c > o, no mask) and the block above (j < o: the coefficients masked
+  // at the adoption; no lane mask has to survive the hand-over).  Team A's accumulators are right as they are and stay.
+  // (Rebuilding them too, to save the branch, left the EMIT kernel with a stack frame for a spilled scalar tuple.)
+  TRUSS_HD void backsub_rebuild(int c) {
+    if (team != 1) return;
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) {
+      double a0 = bz[s], a1 = 0.0;
+#pragma unroll
+      for (int j = W - 1; j >= 0; --j) {
+        const double cf = j >= c ? bc[s][j] : bu[s][j];
+        if (j & 1) a1 = fma(-cf, xs[j], a1);
+        else a0 = fma(-cf, xs[j], a0);
+      }
+      ba[s] = a0 + a1;
     }
   }
   TRUSS_HD void backsub_step(const TopoDev &T, int k, int kk) {
     const int s = kk / WL;
-    double acc0 = bz[s], acc1 = 0.0;
-#pragma unroll
-    for (int m = W - 1; m >= 2; --m) {  // rows k+m, m = W-1 .. 2 (older solutions)
-      const int j = (kk + m) % W;
-      if (m & 1) acc1 = fma(-bc[s][j], xs[j], acc1);
-      else acc0 = fma(-bc[s][j], xs[j], acc0);
-    }
-    const int jn = (kk + 1) % W;        // row k+1: the newest solution
-    double acc = fma(-bc[s][jn], xs[jn], acc0 + acc1);
-    bx = acc * bd[s];
+    bx = ba[s] * bd[s];
   }
-  TRUSS_HD void backsub_share(int kk) {
-    xs[kk] = tb_team_bcast(*this, kk % WL);
-    if (gs == kk % WL) myx[kk / WL] = bx;   // the owner keeps x_k for the block's store
+  // mid: a step of the middle block of the two-sided scheme, where a lane may still hold the solution of the block above
+  // for backsub_flush_mid.  Elsewhere the steps of a block run from its last row to its first, so "every lane at or below
+  // the owner takes bx" leaves the owner's x_k behind as well, and its masks (t < gs) are the ones the adoption has anyway:
+  // WL - 1 lane masks live in the block loop instead of 2 WL - 1.
+  TRUSS_HD void backsub_share(int kk, bool mid = false) {
+    const double x = tb_team_bcast(*this, kk % WL);
+    xs[kk] = x;
+    if (mid ? gs == kk % WL : !(kk % WL < bgs)) myx[kk / WL] = bx;   // the owner keeps x_k for the block's store
+#pragma unroll
+    for (int s = 0; s < RPL; ++s) ba[s] = fma(-bc[s][kk], x, ba[s]);
   }
   // after a block of W steps the owners store their solutions (team-frame rows kb + gs + WL s).  Team B's
   // rows of the middle block (>= KA) were solved by team A and are not written by team B.
@@ -1817,7 +1872,9 @@ struct StepLane {
        of the middle solutions to team B at k = KA - 1 and the rest of that block, instantiated per        \
        c = KA mod W like the merge region above; everything below runs the clean block loop. */            \
     kb_ = ((kend_ - 1) / W_) * W_;                                                  \
+    PH_NS(backsub_begin());                                                         \
     PH_NS(backsub_rows_fetch(T, kb_));                                              \
+    PH_NS(backsub_rows_rcp());                                                      \
     if ((T).nteams == 2 && W_ <= 8) {                                               \
       const int c0_ = (T).KA % W_;                                                  \
       TRUSS_UNROLL                                                                  \
@@ -1828,8 +1885,10 @@ struct StepLane {
           TRUSS_UNROLL                                                              \
           for (int i_ = W_ - 1; i_ >= 0; --i_) {                                    \
             PH_NS(backsub_step(T, (T).KA + i_, (c_ + i_) % W_));                    \
-            PH_NS(backsub_share((c_ + i_) % W_));                                   \
-            if ((c_ + i_) % W_ == 0 && i_ > 0) { /* into the block below */        \
+            PH_NS(backsub_share((c_ + i_) % W_, true));                             \
+            /* the first step behind each fetch: the reciprocals of the rows it asked for */ \
+            if (i_ == W_ - 1 || (c_ + i_) % W_ == W_ - 1) { PH_NS(backsub_rows_rcp()); } \
+            if ((c_ + i_) % W_ == 0 && i_ > 0) { /* into the block below */         \
               kb_ -= W_;                                                            \
               PH_NS(backsub_rows_adopt());                                          \
               PH_NS(backsub_rows_fetch(T, kb_ - W_));                               \
@@ -1838,10 +1897,11 @@ struct StepLane {
           PH_NS(backsub_flush_mid(T));                                              \
           BAR();                                                                    \
           PH_NS(backsub_reload(T));                                                 \
+          if (c_ > 0) { PH_NS(backsub_rebuild(c_)); }                               \
           TRUSS_UNROLL                                                              \
           for (int kk_ = c_ - 1; kk_ >= 0; --kk_) {                                 \
             PH_NS(backsub_step(T, kb_ + kk_, kk_));                                 \
-            PH_NS(backsub_share(kk_));                                              \
+            PH_NS(backsub_share(kk_, true));                                        \
           }                                                                         \
           if (c_ > 0) { PH_NS(backsub_flush(T, kb_)); }                             \
           kb_ -= W_;                                                                \
@@ -1858,10 +1918,12 @@ struct StepLane {
               PH_NS(backsub_flush_mid(T));                                          \
               BAR();                                                                \
               PH_NS(backsub_reload(T));                                             \
+              PH_NS(backsub_rebuild(kk_ + 1));                                      \
             }                                                                       \
             PH_NS(backsub_step(T, kb_ + kk_, kk_));                                 \
-            PH_NS(backsub_share(kk_));                                              \
+            PH_NS(backsub_share(kk_, true));                                        \
           }                                                                         \
+          if (kk_ == W_ / 2) { PH_NS(backsub_rows_rcp()); }                         \
         }                                                                           \
         PH_NS(backsub_flush(T, kb_));                                               \
       }                                                                             \
@@ -1874,6 +1936,7 @@ struct StepLane {
       for (int kk_ = W_ - 1; kk_ >= 0; --kk_) {                                     \
         PH_NS(backsub_step(T, kb_ + kk_, kk_));                                     \
         PH_NS(backsub_share(kk_));                                                  \
+        if (kk_ == W_ / 2) { PH_NS(backsub_rows_rcp()); } /* the next block's rows have landed by now */ \
       }                                                                             \
       PH_NS(backsub_flush(T, kb_));                                                 \
     }                                                                               \

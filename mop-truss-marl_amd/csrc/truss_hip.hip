@@ -25,6 +25,12 @@
 #define TRUSS_HD __device__ __forceinline__
 #define TRUSS_UNROLL _Pragma("unroll")
 #define TB_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+// a value the optimiser cannot trace back to its source: what is computed from it is computed behind this point
+__device__ __forceinline__ int tb_opaque(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+#define TB_OPAQUE(x) tb_opaque(x)
 // result rows are written once and not read again by this launch: streaming (non-temporal) stores leave
 // no dirty lines behind for the end-of-kernel write-back
 #define TB_STREAM_STORE(p, v) __builtin_nontemporal_store((v), (p))
@@ -43,6 +49,22 @@ __device__ __forceinline__ void tb_lds_add(double *p, double v) { unsafeAtomicAd
 // a row holds two teams; quad_perm for 4-lane teams.
 template <int WL, int SRC>
 __device__ __forceinline__ double tb_dpp_bcast(double v) {
+#ifndef TRUSS_BCAST32   // (-DTRUSS_BCAST32: the two 32-bit halves moved separately, for A/B builds)
+  // row_newbcast moves 64 bits at once on gfx950 (v_mov_b64_dpp): one move per team of a row instead of one per half
+  if constexpr (WL == 16 || WL == 8) {
+    // Every lane is written (all rows; bank masks 0x3 and 0xc together), so the `old` operand never shows: a constant, and
+    // the move that sets it up does not wait for v.
+    const long long b = __double_as_longlong(v);
+    long long r;
+    if constexpr (WL == 16) {
+      r = __builtin_amdgcn_update_dpp(0ll, b, 0x150 + SRC, 0xf, 0xf, false);
+    } else {
+      r = __builtin_amdgcn_update_dpp(0ll, b, 0x150 + SRC, 0xf, 0x3, false);
+      r = __builtin_amdgcn_update_dpp(r, b, 0x150 + 8 + SRC, 0xf, 0xc, false);
+    }
+    return __longlong_as_double(r);
+  }
+#endif
   const int lo = __double2loint(v), hi = __double2hiint(v);
   int rlo, rhi;
   if constexpr (WL == 16) {
