@@ -124,6 +124,35 @@ struct GcnLayerDev {
 // vmcnt(0), i.e. for the global loads of the slab after next that are meant to stay in flight across the barrier.
 __device__ __forceinline__ void tg_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// the activation of the C ABI: 0 none, 1 relu, 2 sigmoid (`act` is uniform)
+__device__ __forceinline__ float tg_act(float v, int act) {
+  if (act == 1) v = fmaxf(v, 0.0f);
+  else if (act == 2) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+  return v;
+}
+
+// The first KT terms of row `an` of an adjacency in registers: coefficients cf[], source nodes cj[] (one byte each, n_nodes <= 256;
+// the caller zeroes cj).  adj_row_offset: float offset of the row in adj.  Branch-free, so that the KT table reads and then the KT
+// coefficient reads are in flight together (a dead row / a term past Kn reads entry 0 and is masked afterwards).
+template <int KT>
+__device__ __forceinline__ void tg_load_terms(const int16_t *nbr, const float *adj, long adj_row_offset, int an, int Kn, bool alive,
+                                              float (&cf)[KT], uint32_t (&cj)[(KT + 3) / 4]) {
+  int jj[KT];
+#pragma unroll
+  for (int t = 0; t < KT; ++t) {
+    const bool use = alive && t < Kn;
+    jj[t] = nbr ? (int)nbr[use ? an * Kn + t : 0] : t;
+    jj[t] = use ? jj[t] : -1;
+  }
+#pragma unroll
+  for (int t = 0; t < KT; ++t) {
+    const int j = jj[t];
+    const float c = adj[j < 0 ? 0 : adj_row_offset + j];
+    cf[t] = j < 0 ? 0.0f : c;
+    cj[t >> 2] |= (uint32_t)(j < 0 ? 0 : j) << (8 * (t & 3));            // a missing term re-reads a live row with coefficient 0
+  }
+}
+
 // ---- a consumer of the layer's output in the epilogue of the same launch (truss_gcn_layer_fused) ----
 // The epilogue mode is a template parameter of both kernels; TG_EPI_NONE is the layer as truss_gcn_layer launches it, with the
 // argument block it has always had.  The other two hand the output V = act(acc + bias) over through LDS, one 32-column block
@@ -188,22 +217,8 @@ __device__ __forceinline__ void tg_fused_epilogue(const GcnFusedDev &P, const tg
       const float w = P.w2[ok ? j * C + c : 0];
       sW2[i] = ok ? w : 0.0f;
     }
-    if (kreg2) {                                           // A2's terms of this row: in flight over the rounds below
-      int jj[TG_KREG];
-#pragma unroll
-      for (int t = 0; t < TG_KREG; ++t) {
-        const bool use = alive && t < Kn2;
-        jj[t] = P.nbr2 ? (int)P.nbr2[use ? an * Kn2 + t : 0] : t;
-        jj[t] = use ? jj[t] : -1;
-      }
-#pragma unroll
-      for (int t = 0; t < TG_KREG; ++t) {
-        const int j = jj[t];
-        const float c = P.adj2[j < 0 ? 0 : (long)(g0 + ag) * P.a2_stride + (long)an * N + j];
-        cf2[t] = j < 0 ? 0.0f : c;
-        cj2[t >> 2] |= (uint32_t)(j < 0 ? 0 : j) << (8 * (t & 3));
-      }
-    }
+    if (kreg2)                                             // A2's terms of this row: in flight over the rounds below
+      tg_load_terms<TG_KREG>(P.nbr2, P.adj2, (long)(g0 + ag) * P.a2_stride + (long)an * N, an, Kn2, alive, cf2, cj2);
   }
 
   const int act = P.act;
@@ -219,9 +234,7 @@ __device__ __forceinline__ void tg_fused_epilogue(const GcnFusedDev &P, const tg
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int dr = 8 * (i >> 2) + (i & 3);
-      float v = acc[cb][i] + bc;
-      if (act == 1) v = fmaxf(v, 0.0f);
-      else if (act == 2) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+      const float v = tg_act(acc[cb][i] + bc, act);
       sV[(rbase + dr) * TG_VLD + (lane & 31)] = colok ? v : 0.0f;
       if (store && rbase + dr < rows) po[dr * ostride] = v;
     }
@@ -286,12 +299,45 @@ __device__ __forceinline__ void tg_fused_epilogue(const GcnFusedDev &P, const tg
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int j = ah * 4 + q;
-        if (j < c2) {
-          float v = s[q] + (P.bias2 ? P.bias2[j] : 0.0f);
-          if (act2 == 1) v = fmaxf(v, 0.0f);
-          else if (act2 == 2) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-          po2[j] = v;
+        if (j < c2) po2[j] = tg_act(s[q] + (P.bias2 ? P.bias2[j] : 0.0f), act2);
+      }
+    }
+  }
+}
+
+// The plain epilogue of the float32 layer kernel (truss_gcn_bf3_body.h has the same statements written out): accumulator
+// register i of a lane = row 8 (i / 4) + 4 (l / 32) + i % 4, column l % 32 of the 32 x 32 block.
+// Per column block: (accumulate: the 16 old values, from clamped addresses, in flight together) -> bias, activation
+// -> 16 predicated stores; 32 lanes write 128 contiguous bytes of a row.  `act` / `accumulate` are uniform.
+template <int CB>
+__device__ __forceinline__ void tg_store_epilogue(const GcnLayerDev &P, const tg_f16 (&acc)[CB], int rows, long row0, int lane, int wave) {
+  const int C = P.C, act = P.act;
+  const bool accum = P.accumulate != 0;
+  const int rbase = wave * 32 + 4 * (lane >> 5);            // row of accumulator register 0; register i: + 8 (i / 4) + i % 4
+  const long ostride = P.out_stride;
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) {
+    const int col = cb * 32 + (lane & 31);
+    const bool colok = col < C;
+    const float bc = (P.bias && colok) ? P.bias[col] : 0.0f;
+    float *po = P.out + (row0 + rbase) * ostride + (colok ? col : 0);
+#pragma unroll
+    for (int i0 = 0; i0 < 16; i0 += 8) {
+      float old[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) old[i] = 0.0f;
+      if (accum) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int dr = 8 * ((i0 + i) >> 2) + ((i0 + i) & 3);
+          old[i] = po[(rbase + dr < rows ? dr : 0 - rbase) * ostride];      // a dead row re-reads the tile's first row
         }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int dr = 8 * ((i0 + i) >> 2) + ((i0 + i) & 3);
+        const float v = tg_act(acc[cb][i0 + i] + bc, act) + old[i];
+        if (colok && rbase + dr < rows) po[dr * ostride] = v;
       }
     }
   }
@@ -331,22 +377,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
   uint32_t cj[(TG_KREG + 3) / 4] = {};                     // source nodes of the terms, one byte each (n_nodes <= 256)
   const int abase = ((alive ? ag * N : 0)) * TG_LD + ak;   // float offset of the graph's first row (this thread's eight k's) in sXraw
   if (kreg) {
-    // branch-free, so that the nine table reads and then the nine coefficient reads are in flight together (a dead row / a term
-    // past Kn reads entry 0 and is masked afterwards)
-    int jj[TG_KREG];
-#pragma unroll
-    for (int t = 0; t < TG_KREG; ++t) {
-      const bool use = alive && t < Kn;
-      jj[t] = P.nbr ? (int)P.nbr[use ? an * Kn + t : 0] : t;
-      jj[t] = use ? jj[t] : -1;
-    }
-#pragma unroll
-    for (int t = 0; t < TG_KREG; ++t) {
-      const int j = jj[t];
-      const float c = P.adj[j < 0 ? 0 : (long)(g0 + ag) * P.a_stride + (long)an * N + j];
-      cf[t] = j < 0 ? 0.0f : c;
-      cj[t >> 2] |= (uint32_t)(j < 0 ? 0 : j) << (8 * (t & 3));          // a missing term re-reads a live row with coefficient 0
-    }
+    tg_load_terms<TG_KREG>(P.nbr, P.adj, (long)(g0 + ag) * P.a_stride + (long)an * N, an, Kn, alive, cf, cj);
   } else {
     for (int i = tid; i < N * Kn; i += NT) sIdx[i] = P.nbr ? P.nbr[i] : (int16_t)(i % Kn);
     for (int i = tid; i < rows * Kn; i += NT) {
@@ -563,44 +594,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
 
   if constexpr (EPI != TG_EPI_NONE) {                      // a consumer of the output in the same launch; its barriers are inside
     tg_fused_epilogue<NW, CB, EPI>(P, acc, tg_smem, rows, row0, g0, ng);
-    return;
-  }
-
-  // ---- epilogue: accumulator register i of a lane = row 8 (i / 4) + 4 (l / 32) + i % 4, column l % 32 of the 32 x 32 block.
-  // Per column block: (accumulate: the 16 old values, from clamped addresses, in flight together) -> bias, activation -> 16
-  // predicated stores; 32 lanes write 128 contiguous bytes of a row.  `act` / `accumulate` are uniform.
-  const int act = P.act;
-  const bool accum = P.accumulate != 0;
-  const int rbase = wave * 32 + 4 * (lane >> 5);            // row of accumulator register 0; register i: + 8 (i / 4) + i % 4
-  const long ostride = P.out_stride;
-#pragma unroll
-  for (int cb = 0; cb < CB; ++cb) {
-    const int col = cb * 32 + (lane & 31);
-    const bool colok = col < C;
-    const float bc = (P.bias && colok) ? P.bias[col] : 0.0f;
-    float *po = P.out + (row0 + rbase) * ostride + (colok ? col : 0);
-#pragma unroll
-    for (int i0 = 0; i0 < 16; i0 += 8) {
-      float old[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) old[i] = 0.0f;
-      if (accum) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int dr = 8 * ((i0 + i) >> 2) + ((i0 + i) & 3);
-          old[i] = po[(rbase + dr < rows ? dr : 0 - rbase) * ostride];      // a dead row re-reads the tile's first row
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int dr = 8 * ((i0 + i) >> 2) + ((i0 + i) & 3);
-        float v = acc[cb][i0 + i] + bc;
-        if (act == 1) v = fmaxf(v, 0.0f);
-        else if (act == 2) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        v += old[i];
-        if (colok && rbase + dr < rows) po[dr * ostride] = v;
-      }
-    }
+  } else {
+    tg_store_epilogue<CB>(P, acc, rows, row0, lane, wave);
   }
 }
 
@@ -666,249 +661,17 @@ typedef __attribute__((address_space(1))) const void tg_glob_void;
 
 // KT: neighbourhood terms per row that are gathered (6: the grid trusses -- a node joins at most five others; 9: any pattern the
 // register path takes).  Terms past k_nbr have coefficient 0, but every one of them is two 16-byte LDS reads per slab and thread.
+//
+// The layer's text is truss_gcn_bf3_body.h, included as the body of two kernels: truss_gcn_layer_bf3_kernel runs it once,
+// truss_gcn_group_bf3_kernel (truss_gcn_group.h) once per step of a chain.  Keep it an include: as a __device__ function the text is
+// simplified on its own before it is inlined, the T = 2 slab loop changes and ran 0.9 % slower.  Its term load and store epilogue
+// are written out and are not calls of tg_load_terms / tg_store_epilogue: with the two calls the slab loop stayed the parent's, the
+// code round it did not, and T = 2 ran 0.8 % slower; written out (and with tg_act, which changes nothing) the plain and POOL
+// kernels are instruction for instruction what they were before the text was shared (profiles/r16/README.md sections 1 and 3).
 template <int NW, int KT, int EPI = TG_EPI_NONE, int T = 3>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void truss_gcn_layer_bf3_kernel(const typename TgArgs<EPI>::type P, const uint16_t *__restrict__ ws, int KP) {
-  constexpr int MT = 32 * NW, NT = 64 * NW, CB = 7, WROWS = 32 * CB;
-  static_assert(WROWS == TG_CP, "split-weight image rows");
-  static_assert(T >= 1 && T <= 3, "bf16 terms per operand");
-  extern __shared__ __attribute__((aligned(16))) char tg_smem[];
-  float *sXraw = (float *)tg_smem;                                   // [MT][TG_LD] float32 raw input rows of a slab
-  char *sXs = tg_smem + MT * TG_LD * 4;                              // [2][T][MT][32 B]    split aggregated rows (MFMA A operand)
-  char *sWs = sXs + 2 * T * MT * 32;                                 // [2][T][WROWS][32 B] split W slab, [col][k]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int N = P.N, Kn = P.Kn, K = P.K, C = P.C;
-  const int g0 = blockIdx.x * P.GB;
-  const int ng = (P.B - g0 < P.GB) ? P.B - g0 : P.GB;
-  const int rows = ng * N;
-  const long row0 = (long)g0 * N;
-
-  const int ar = tid >> 1, ah = tid & 1, ak = ah * 8;
-  const int ag = ar / N, an = ar - ag * N;
-  const bool alive = ar < rows;
-  float cf[KT];
-  uint32_t cj[(KT + 3) / 4] = {};
-  const int abase = ((alive ? ag * N : 0)) * TG_LD + ak;
-  {
-    int jj[KT];
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-      const bool use = alive && t < Kn;
-      jj[t] = P.nbr ? (int)P.nbr[use ? an * Kn + t : 0] : t;
-      jj[t] = use ? jj[t] : -1;
-    }
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-      const int j = jj[t];
-      const float c = P.adj[j < 0 ? 0 : (long)(g0 + ag) * P.a_stride + (long)an * N + j];
-      cf[t] = j < 0 ? 0.0f : c;
-      cj[t >> 2] |= (uint32_t)(j < 0 ? 0 : j) << (8 * (t & 3));
-    }
-  }
-
-  // staging.  X slab: two 16-byte chunks per thread through registers, as in the float32 kernel.  W slab (T terms x 224 cols x two
-  // 16-byte halves = 7 T wave-instructions of 1 KB, 21 for T = 3): LDS-DMA (global_load_lds_dwordx4) -- lane i of instruction j fetches the chunk
-  // that belongs at LDS position 64 j + i of the (swizzled) image, no registers, no ds_write.  Every wave issues exactly WD of
-  // them (instruction numbers past the last repeat it), so that "at most WD vector-memory operations outstanding" means "everything
-  // older than the last W slab has landed".
-  constexpr int XC = MT * 4 / NT;                                    // = 2
-  constexpr int WI = T * WROWS * 2 / 64;                             // = 7 T wave-instructions per slab: 21, 14, 7
-  constexpr int WD = (WI + NW - 1) / NW;                             // per wave, NW = 4 / 8: 6 / 3 (T = 3), 4 / 2 (T = 2), 2 / 1 (T = 1)
-  static_assert(WI == 7 * T && WI % T == 0 && WD * NW >= WI && (WD - 1) * NW < WI, "LDS-DMA instructions of a W slab");
-  const int uwave = __builtin_amdgcn_readfirstlane(wave);
-  tg_f4 rx[XC];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int c = 0; c < XC; ++c) {
-      const int q = tid + c * NT, r = q >> 2, kk = k0 + (q & 3) * 4;
-      const bool ok = r < rows && kk < K;
-      const tg_f4 ld = *(const tg_f4 *)(ok ? P.x + (row0 + r) * P.x_stride + kk : P.x);
-      const tg_f4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-      rx[c] = ok ? ld : z;
-    }
-  };
-  auto stash_x = [&]() {
-#pragma unroll
-    for (int c = 0; c < XC; ++c) {
-      const int q = tid + c * NT;
-      *(tg_f4 *)(sXraw + (q >> 2) * TG_LD + (q & 3) * 4) = rx[c];
-    }
-  };
-  auto dma_w = [&](int k0, int buf) {                                // slabs past the end of K read the zero padding of the last one
-    const int kc = k0 < KP ? k0 : KP - TG_KS;                        // (a slab past the end is never multiplied: any valid address)
-#pragma unroll
-    for (int c = 0; c < WD; ++c) {
-      int j = uwave + c * NW;
-      j = j < WI ? j : WI - 1;
-      const int t = j / (WI / T), rem = (j % (WI / T)) * 64 + lane;  // term; position inside the term's [224][2] image
-      const int col = rem >> 1, h = (rem & 1) ^ ((col >> 3) & 1);
-      const uint16_t *src = ws + ((long)t * TG_CP + col) * KP + kc + h * 8;
-      __builtin_amdgcn_global_load_lds((tg_glob_void *)src, (tg_lds_void *)(sWs + (buf * T * WROWS * 2 + j * 64) * 16), 16, 0, 0);
-    }
-  };
-  auto gather = [&](int t_lo, int t_hi, tg_f4 &a0, tg_f4 &a1) {
-#pragma unroll
-    for (int tt = t_lo; tt < t_hi; ++tt) {
-      const float *src = sXraw + abase + (int)((cj[tt >> 2] >> (8 * (tt & 3))) & 255u) * TG_LD;
-      a0 += cf[tt] * *(const tg_f4 *)src;
-      a1 += cf[tt] * *(const tg_f4 *)(src + 4);
-    }
-  };
-  auto put_split = [&](int buf, const tg_f4 a0, const tg_f4 a1) {    // this thread's eight k of row ar, the first T terms
-    float r[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-      *(tg_u4 *)(sXs + (((buf * T + t) * MT + ar) * 2 + (ah ^ ((ar >> 3) & 1))) * 16) = tg_split_term(r, t == T - 1);
-  };
-
-  tg_f16 acc[CB];
-#pragma unroll
-  for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[cb][i] = 0.0f;
-  const int mrow = wave * 32 + (lane & 31), mh = lane >> 5, mcol = lane & 31;
-
-  // Order of the vector-memory operations of a wave (they complete in order): [W 0] [X 0] [W 1] [X 1] | loop s: [X s+2] [W s+2].
-  // Waiting for the registers of X s+2 (stash_x, end of iteration s) therefore implies that W s+1 has landed; the explicit
-  // "vmcnt(WD)" in front of the top barrier says the same thing for the reader of this code.  Every wave issues exactly WD LDS-DMA
-  // instructions per W slab, whatever T is, and the immediate IS the constant WD: at most the youngest W slab is outstanding.
-  const int nslab = (K + TG_KS - 1) / TG_KS;
-  dma_w(0, 0);
-  fetch(0);
-  stash_x();
-  dma_w(TG_KS, 1);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WD) : "memory");
-  tg_lds_barrier();
-  fetch(TG_KS);
-  {
-    tg_f4 a0 = {0.0f, 0.0f, 0.0f, 0.0f}, a1 = a0;
-    gather(0, KT, a0, a1);
-    put_split(0, a0, a1);
-  }
-  tg_lds_barrier();
-  stash_x();
-#ifdef TRUSS_GCN_STAMPS
-  unsigned long long acc_t[4] = {0, 0, 0, 0};
-  const unsigned long long t_loop0 = clock64();
-#endif
-  for (int s = 0; s < nslab; ++s) {
-    TG_T(ta);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WD) : "memory");
-    tg_lds_barrier();                                                // X'[s], raw slab s + 1 and W slab s are in LDS
-    TG_T(tb);
-    const int buf = s & 1;
-    fetch((s + 2) * TG_KS);
-    tg_bf8 xa[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) xa[t] = *(const tg_bf8 *)(sXs + (((buf * T + t) * MT + mrow) * 2 + (mh ^ ((mrow >> 3) & 1))) * 16);
-    tg_f4 a0 = {0.0f, 0.0f, 0.0f, 0.0f}, a1 = a0;
-    if constexpr (T == 3) {
-#pragma unroll
-      for (int cb = 0; cb < CB; ++cb) {
-        const int col = cb * 32 + mcol;
-        tg_bf8 wb[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) wb[t] = *(const tg_bf8 *)(sWs + (((buf * 3 + t) * WROWS + col) * 2 + (mh ^ ((col >> 3) & 1))) * 16);
-        if (cb * 2 < KT) gather(cb * 2, cb * 2 + 2 < KT ? cb * 2 + 2 : KT, a0, a1);   // two terms between the MFMAs of each of the first column blocks
-        // small partial products first
-        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[2], wb[0], acc[cb], 0, 0, 0);
-        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1], wb[1], acc[cb], 0, 0, 0);
-        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[2], acc[cb], 0, 0, 0);
-        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1], wb[0], acc[cb], 0, 0, 0);
-        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[1], acc[cb], 0, 0, 0);
-        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[0], acc[cb], 0, 0, 0);
-      }
-    } else {
-      // T < 3.  With fewer MFMAs to place between them the scheduler would issue the operand reads of all seven column blocks and
-      // every gather read at the top of the slab -- more live registers than the 256 of two waves per SIMD, i.e. spills.  So the
-      // column blocks go in four regions {0, 1} {2, 3} {4, 5} {6} with a scheduling barrier behind each: the B operands of the next
-      // region are requested before the MFMAs of the present one (in flight over them), nothing moves across a region's end.
-      tg_bf8 wb[CB][T];
-      auto load_wb = [&](int lo, int hi) {
-#pragma unroll
-        for (int cb = lo; cb < hi; ++cb) {
-          const int col = cb * 32 + mcol;
-#pragma unroll
-          for (int t = 0; t < T; ++t) wb[cb][t] = *(const tg_bf8 *)(sWs + (((buf * T + t) * WROWS + col) * 2 + (mh ^ ((col >> 3) & 1))) * 16);
-        }
-      };
-      load_wb(0, 2);
-#pragma unroll
-      for (int r = 0; r < (CB + 1) / 2; ++r) {
-        const int lo = 2 * r, hi = lo + 2 < CB ? lo + 2 : CB;
-        load_wb(hi, hi + 2 < CB ? hi + 2 : CB);
-#pragma unroll
-        for (int cb = lo; cb < hi; ++cb) {
-          if (cb * 2 < KT) gather(cb * 2, cb * 2 + 2 < KT ? cb * 2 + 2 : KT, a0, a1);
-          // the products x_i w_j with i + j <= T - 1, small partial products first
-          if constexpr (T == 2) {
-            acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[1], wb[cb][0], acc[cb], 0, 0, 0);
-            acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[cb][1], acc[cb], 0, 0, 0);
-          }
-          acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0], wb[cb][0], acc[cb], 0, 0, 0);
-          // (nine terms, two products: the four gather terms of a region in flight together are three registers too many for the
-          // head epilogue's instantiation -- the two column blocks of a region keep their gathers apart)
-          if constexpr (T == 2 && KT > 6) __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    put_split(buf ^ 1, a0, a1);                                      // behind the last operand read of this slab
-    TG_T(tc);
-    tg_lds_barrier();                                                // everybody is done with sXraw (slab s + 1) and with sWs / sXs [buf]
-    TG_T(td);
-    dma_w((s + 2) * TG_KS, buf);                                     // W slab s + 2 -> sWs[buf]
-    stash_x();                                                       // raw slab s + 2 -> sXraw
-#ifdef TRUSS_GCN_STAMPS
-    const unsigned long long te = clock64();
-    acc_t[0] += tb - ta; acc_t[1] += tc - tb; acc_t[2] += td - tc; acc_t[3] += te - td;
-#endif
-  }
-#ifdef TRUSS_GCN_STAMPS
-  if (blockIdx.x == 0 && tid == 0) {
-    for (int i = 0; i < 4; ++i) g_gcn_stamps[i] = acc_t[i];
-    g_gcn_stamps[4] = clock64() - t_loop0;
-    g_gcn_stamps[5] = nslab;
-  }
-#endif
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // no LDS-DMA may still be in flight when the workgroup ends
-  if constexpr (EPI != TG_EPI_NONE) {
-    tg_fused_epilogue<NW, CB, EPI>(P, acc, tg_smem, rows, row0, g0, ng);
-    return;
-  }
-
-  const int act = P.act;
-  const bool accum = P.accumulate != 0;
-  const int rbase = wave * 32 + 4 * (lane >> 5);
-  const long ostride = P.out_stride;
-#pragma unroll
-  for (int cb = 0; cb < CB; ++cb) {
-    const int col = cb * 32 + (lane & 31);
-    const bool colok = col < C;
-    const float bc = (P.bias && colok) ? P.bias[col] : 0.0f;
-    float *po = P.out + (row0 + rbase) * ostride + (colok ? col : 0);
-#pragma unroll
-    for (int i0 = 0; i0 < 16; i0 += 8) {
-      float old[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) old[i] = 0.0f;
-      if (accum) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int dr = 8 * ((i0 + i) >> 2) + ((i0 + i) & 3);
-          old[i] = po[(rbase + dr < rows ? dr : 0 - rbase) * ostride];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int dr = 8 * ((i0 + i) >> 2) + ((i0 + i) & 3);
-        float v = acc[cb][i0 + i] + bc;
-        if (act == 1) v = fmaxf(v, 0.0f);
-        else if (act == 2) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        v += old[i];
-        if (colok && rbase + dr < rows) po[dr * ostride] = v;
-      }
-    }
-  }
+  const int tid = threadIdx.x;
+#include "truss_gcn_bf3_body.h"
 }
 
 static size_t tg_lds_bytes(int NW, int CB, int N, int Kn) {
@@ -947,15 +710,23 @@ static GcnFusedDev tg_fused_dev(const truss_gcn_layer_args_t *a, const truss_gcn
   return P;
 }
 
+// LDS of truss_gcn_bf3_body.h in a kernel <NW, KT, EPI, T>: the slab loop's footprint shrinks with T (77 824 / 55 296 / 32 768
+// bytes at NW = 4); a fused epilogue reuses it and needs tg_epi_lds_bytes(NW), which is the larger one only for T = 1 at NW = 8.
+static size_t tg_bf3_lds_bytes(int NW, int T, bool fused) {
+  const size_t MT = 32 * (size_t)NW;
+  const size_t lds = MT * TG_LD * 4 + 2 * T * MT * 32 + 2 * T * TG_CP * 32;
+  return fused && lds < tg_epi_lds_bytes(NW) ? tg_epi_lds_bytes(NW) : lds;
+}
+
+// the run-time number of bf16 terms as the last template argument of launch<EPI, T>(...): tg_launch_bf3, tgg_launch
+#define TG_BY_TERMS(terms, launch, epi, ...) \
+  ((terms) == 3 ? launch<epi, 3>(__VA_ARGS__) : (terms) == 2 ? launch<epi, 2>(__VA_ARGS__) : launch<epi, 1>(__VA_ARGS__))
+
 // The launch of truss_gcn_layer_bf3_kernel<NW, KT, EPI, T> for a checked layer (every entry that takes split weights ends here).
-// LDS: the slab loop's footprint shrinks with T (77 824 / 55 296 / 32 768 bytes at NW = 4); a fused epilogue reuses it and
-// needs tg_epi_lds_bytes(NW), which is the larger one only for T = 1 at NW = 8.
 template <int EPI, int T>
 static int tg_launch_bf3(const typename TgArgs<EPI>::type &P, int NW, const uint16_t *ws, int k_in, hipStream_t st) {
   const int KP = (k_in + 15) & ~15;
-  const size_t MT = 32 * (size_t)NW;
-  size_t lds = MT * TG_LD * 4 + 2 * T * MT * 32 + 2 * T * 224 * 32;
-  if (EPI != TG_EPI_NONE && lds < tg_epi_lds_bytes(NW)) lds = tg_epi_lds_bytes(NW);
+  const size_t lds = tg_bf3_lds_bytes(NW, T, EPI != TG_EPI_NONE);
   const unsigned grid = (unsigned)((P.B + P.GB - 1) / P.GB);
 #define TG_LAUNCH3(nw, kt)                                                                                                        \
   do {                                                                                                                            \
@@ -969,28 +740,21 @@ static int tg_launch_bf3(const typename TgArgs<EPI>::type &P, int NW, const uint
   return TRUSS_OK;
 }
 
-extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
-  if (!a) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: NULL argument");
-  if (int rc = tb_gcn_layer_check(a, "truss_gcn_layer", 256, 0, false)) return rc;
-  if (a->n_batch == 0) return TRUSS_OK;
-  const int NW = a->n_nodes > 128 ? 8 : 4;
-  const GcnLayerDev P = tg_layer_dev(a, 32 * NW);
-  const int CB = a->c_out <= 32 ? 1 : 7;
-  hipStream_t st = (hipStream_t)stream;
-  if (a->w_bf16x3) {
-    // product on the bf16 matrix cores at float32 accuracy (see truss_gcn_layer_bf3_kernel)
-    if (int rc = tb_gcn_bf16x3_check(a)) return rc;
-    if (int rc = tg_launch_bf3<TG_EPI_NONE, 3>(P, NW, a->w_bf16x3, a->k_in, st)) return rc;
-    return tb_launched("gcn layer (bf16x3) kernel launch failed: ");
-  }
-  const size_t lds = tg_lds_bytes(NW, CB, a->n_nodes, P.Kn);
-  if (lds > 160 * 1024) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer: tile does not fit the LDS");
-  const unsigned grid = (unsigned)((a->n_batch + P.GB - 1) / P.GB);
-#define TG_LAUNCH(nw, cb, vec)                                                                              \
-  do {                                                                                                      \
-    static TbLdsOptIn optin;                                                                                \
-    if (int rc = optin.ensure((const void *)truss_gcn_layer_kernel<nw, cb, vec>)) return rc;                \
-    hipLaunchKernelGGL((truss_gcn_layer_kernel<nw, cb, vec>), dim3(grid), dim3(64 * nw), lds, st, P);       \
+// The launch of truss_gcn_layer_kernel<NW, CB, VEC, EPI> for a checked layer, shaped like tg_launch_bf3.
+template <int EPI>
+static int tg_launch_f32(const typename TgArgs<EPI>::type &P, int NW, hipStream_t st) {
+  const bool fused = EPI != TG_EPI_NONE;
+  const int CB = P.C <= 32 ? 1 : 7;
+  size_t lds = tg_lds_bytes(NW, CB, P.N, P.Kn);
+  if (fused && lds < tg_epi_lds_bytes(NW)) lds = tg_epi_lds_bytes(NW);
+  if (lds > 160 * 1024)
+    return tb_fail(TRUSS_EUNSUPPORTED, fused ? "truss_gcn_layer_fused: tile does not fit the LDS" : "truss_gcn_layer: tile does not fit the LDS");
+  const unsigned grid = (unsigned)((P.B + P.GB - 1) / P.GB);
+#define TG_LAUNCH(nw, cb, vec)                                                                                   \
+  do {                                                                                                           \
+    static TbLdsOptIn optin;                                                                                     \
+    if (int rc = optin.ensure((const void *)truss_gcn_layer_kernel<nw, cb, vec, EPI>)) return rc;                \
+    hipLaunchKernelGGL((truss_gcn_layer_kernel<nw, cb, vec, EPI>), dim3(grid), dim3(64 * nw), lds, st, P);       \
   } while (0)
   const bool vec = P.x_vec && P.w_vec;
   if (NW == 4 && CB == 7) { if (vec) TG_LAUNCH(4, 7, true); else TG_LAUNCH(4, 7, false); }
@@ -998,6 +762,23 @@ extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
   else if (CB == 7) { if (vec) TG_LAUNCH(8, 7, true); else TG_LAUNCH(8, 7, false); }
   else { if (vec) TG_LAUNCH(8, 1, true); else TG_LAUNCH(8, 1, false); }
 #undef TG_LAUNCH
+  return TRUSS_OK;
+}
+
+extern "C" int truss_gcn_layer(const truss_gcn_layer_args_t *a, void *stream) {
+  if (!a) return tb_fail(TRUSS_EINVAL, "truss_gcn_layer: NULL argument");
+  if (int rc = tb_gcn_layer_check(a, "truss_gcn_layer", 256, 0, false)) return rc;
+  if (a->n_batch == 0) return TRUSS_OK;
+  const int NW = a->n_nodes > 128 ? 8 : 4;
+  const GcnLayerDev P = tg_layer_dev(a, 32 * NW);
+  hipStream_t st = (hipStream_t)stream;
+  if (a->w_bf16x3) {
+    // product on the bf16 matrix cores at float32 accuracy (see truss_gcn_layer_bf3_kernel)
+    if (int rc = tb_gcn_bf16x3_check(a)) return rc;
+    if (int rc = tg_launch_bf3<TG_EPI_NONE, 3>(P, NW, a->w_bf16x3, a->k_in, st)) return rc;
+    return tb_launched("gcn layer (bf16x3) kernel launch failed: ");
+  }
+  if (int rc = tg_launch_f32<TG_EPI_NONE>(P, NW, st)) return rc;
   return tb_launched("gcn layer kernel launch failed: ");
 }
 
@@ -1012,32 +793,13 @@ extern "C" int truss_gcn_layer_fused(const truss_gcn_layer_args_t *a, const trus
   const bool head = e->kind == TRUSS_GCN_EPI_HEAD;
   const int NW = a->n_nodes > 128 ? 8 : 4;
   const GcnFusedDev P = tg_fused_dev(a, e, 32 * NW);
-  const int CB = a->c_out <= 32 ? 1 : 7;
-  const size_t lds_epi = tg_epi_lds_bytes(NW);
-  const unsigned grid = (unsigned)((a->n_batch + P.GB - 1) / P.GB);
   hipStream_t st = (hipStream_t)stream;
   if (a->w_bf16x3) {
     if (int rc = head ? tg_launch_bf3<TG_EPI_HEAD, 3>(P, NW, a->w_bf16x3, a->k_in, st) : tg_launch_bf3<TG_EPI_POOL, 3>(P, NW, a->w_bf16x3, a->k_in, st))
       return rc;
     return tb_launched("gcn fused layer (bf16x3) kernel launch failed: ");
   }
-  size_t lds = tg_lds_bytes(NW, CB, a->n_nodes, P.Kn);
-  if (lds < lds_epi) lds = lds_epi;
-  if (lds > 160 * 1024) return tb_fail(TRUSS_EUNSUPPORTED, "truss_gcn_layer_fused: tile does not fit the LDS");
-#define TG_LAUNCHE(nw, cb, vec, epi)                                                                             \
-  do {                                                                                                           \
-    static TbLdsOptIn optin;                                                                                     \
-    if (int rc = optin.ensure((const void *)truss_gcn_layer_kernel<nw, cb, vec, epi>)) return rc;                \
-    hipLaunchKernelGGL((truss_gcn_layer_kernel<nw, cb, vec, epi>), dim3(grid), dim3(64 * nw), lds, st, P);       \
-  } while (0)
-#define TG_LAUNCH(nw, cb, vec) do { if (head) TG_LAUNCHE(nw, cb, vec, TG_EPI_HEAD); else TG_LAUNCHE(nw, cb, vec, TG_EPI_POOL); } while (0)
-  const bool vec = P.x_vec && P.w_vec;
-  if (NW == 4 && CB == 7) { if (vec) TG_LAUNCH(4, 7, true); else TG_LAUNCH(4, 7, false); }
-  else if (NW == 4) { if (vec) TG_LAUNCH(4, 1, true); else TG_LAUNCH(4, 1, false); }
-  else if (CB == 7) { if (vec) TG_LAUNCH(8, 7, true); else TG_LAUNCH(8, 7, false); }
-  else { if (vec) TG_LAUNCH(8, 1, true); else TG_LAUNCH(8, 1, false); }
-#undef TG_LAUNCH
-#undef TG_LAUNCHE
+  if (int rc = head ? tg_launch_f32<TG_EPI_HEAD>(P, NW, st) : tg_launch_f32<TG_EPI_POOL>(P, NW, st)) return rc;
   return tb_launched("gcn fused layer kernel launch failed: ");
 }
 
@@ -1053,17 +815,14 @@ extern "C" int truss_gcn_layer_terms(const truss_gcn_layer_args_t *a, const trus
   const int NW = a->n_nodes > 128 ? 8 : 4;
   hipStream_t st = (hipStream_t)stream;
   int rc;
-#define TG_TERMS(epi, P) (terms == 3 ? tg_launch_bf3<epi, 3>(P, NW, a->w_bf16x3, a->k_in, st)     \
-                          : terms == 2 ? tg_launch_bf3<epi, 2>(P, NW, a->w_bf16x3, a->k_in, st)   \
-                                       : tg_launch_bf3<epi, 1>(P, NW, a->w_bf16x3, a->k_in, st))
   if (!e) {
     const GcnLayerDev P = tg_layer_dev(a, 32 * NW);
-    rc = TG_TERMS(TG_EPI_NONE, P);
+    rc = TG_BY_TERMS(terms, tg_launch_bf3, TG_EPI_NONE, P, NW, a->w_bf16x3, a->k_in, st);
   } else {
     const GcnFusedDev P = tg_fused_dev(a, e, 32 * NW);
-    rc = e->kind == TRUSS_GCN_EPI_HEAD ? TG_TERMS(TG_EPI_HEAD, P) : TG_TERMS(TG_EPI_POOL, P);
+    rc = e->kind == TRUSS_GCN_EPI_HEAD ? TG_BY_TERMS(terms, tg_launch_bf3, TG_EPI_HEAD, P, NW, a->w_bf16x3, a->k_in, st)
+                                       : TG_BY_TERMS(terms, tg_launch_bf3, TG_EPI_POOL, P, NW, a->w_bf16x3, a->k_in, st);
   }
-#undef TG_TERMS
   if (rc) return rc;
   return tb_launched("gcn layer (bf16 terms) kernel launch failed: ");
 }

@@ -288,10 +288,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TGL_WAVES_P
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = cl + 4 * q + j;
-      float t = v[j] + ((P.bias && c < C) ? P.bias[c0 + c] : 0.0f);
-      if (act == 1) t = fmaxf(t, 0.0f);
-      else if (act == 2) t = __builtin_amdgcn_rcpf(1.0f + __expf(-t));
-      v[j] = t;
+      v[j] = tg_act(v[j] + ((P.bias && c < C) ? P.bias[c0 + c] : 0.0f), act);
     }
     if (whole) {
       *(tg_f4 *)(po + 4 * q) = v;
