@@ -612,6 +612,37 @@ typedef struct truss_gcn_level_bwd {
 } truss_gcn_level_bwd_t;
 int truss_gcn_level_backward(const truss_gcn_layer_args_t *layers, int32_t n_layers, const truss_gcn_level_bwd_t *bwd, void *stream);
 
+/* The NEIGHBOUR SUMS of a level through the node table, for graphs beyond the 64 nodes of the two entries above: for up to
+ * TRUSS_GCN_AGG_MAX independent items per launch (more run as consecutive launches, as in truss_gcn_level), per graph g and row i
+ *   transpose == 0:  y[g,i] = sum_t adj[g][i][j_t] x[g,j_t]        transpose != 0:  y[g,i] = sum_t adj[g][j_t][i] x[g,j_t]
+ * over the entries j_t = nbr[i][t] >= 0 of row i of the table, in table order, float32 fmaf from 0.  The first is A x for an
+ * adjacency that is zero outside the table; the second is A^T x exactly when the table is structurally symmetric (j in row i iff
+ * i in row j) -- which this entry cannot check on a device table and does not; the caller does (truss2D_RL.NodePattern).
+ * replaces: the N x N products X' = A X and dX = A^T (dZ W) of the MADDPG update (truss2D_RL.py:561-689) where a truss node has at
+ * most 9 neighbours: 2 k N n_ch flop per graph instead of 2 N^2 n_ch, and no [n B, N, N] stack of adjacencies.  The dense products
+ * of the level (X' W^T, dZ^T X', dZ W) stay with the library.
+ *   x    [n_batch * n_nodes][n_ch], rows contiguous            y    the same shape; must not overlap x
+ *   adj  dense [n_nodes][n_nodes] per graph, a_batch_stride floats apart (0: one adjacency for all); read only at the table's columns
+ *   nbr  [n_nodes][k_nbr] int16, -1 = no entry (as for truss_gcn_aggregate_sparse; entries need not be ascending)
+ * n_nodes 1..32767, k_nbr 1..16, any n_ch >= 1: 16-byte accesses where n_ch % 4 == 0 and x / y are 16-byte aligned, element by
+ * element otherwise (the update has n_ch of 2, 3, 13 and 4: actions, node features, the front).  An item with n_batch == 0 passes
+ * unread; n_items == 0: TRUSS_OK, no launch.  TRUSS_EINVAL: a NULL pointer, a wrong struct_size, sizes outside the above, y
+ * overlapping x -- nothing is launched or written on any refusal.  The items' descriptors travel in the kernel arguments: the entry
+ * allocates nothing, does not synchronise; capturable.  Every output element has one owner and a fixed order of summation (no
+ * atomics): results are bitwise reproducible from call to call.  Device pointers.  Optional entry of ABI version 3 (a library may
+ * lack it). */
+#define TRUSS_GCN_AGG_MAX 24   /* items per launch */
+typedef struct truss_gcn_agg {
+  uint32_t struct_size;
+  const float *x;
+  const float *adj;
+  int64_t a_batch_stride;
+  const int16_t *nbr;
+  float *y;
+  int32_t n_batch, n_nodes, n_ch, k_nbr, transpose;
+} truss_gcn_agg_t;
+int truss_gcn_level_aggregate(const truss_gcn_agg_t *items, int32_t n_items, void *stream);
+
 /* w [c_out <= 224][k_in] float32 -> w_bf16x3 [3][224][kp] bfloat16 bit patterns (kp = (k_in + 15) & ~15; rows >= c_out and columns >=
  * k_in are written as zeros: the layer kernel reads whole 224 x 16 slabs by LDS-DMA): the exact
  * three-term split the bf16x3 path of truss_gcn_layer reads.  Once per weight version; device pointers, 16-byte aligned output. */

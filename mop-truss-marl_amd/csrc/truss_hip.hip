@@ -9,7 +9,8 @@
 // This file holds the step, rollout and observation kernels and their launch glue only.  Every other kernel family has a
 // header of its own, included at the end: truss_gcn.h, truss_gcn_level.h, truss_gcn_level_bwd.h, truss_replay.h, truss_front.h
 // (Pareto front + hypervolume), truss_reward.h (the difference reward), truss_archive.h (the archive update),
-// truss_pairs.h (the set-up of a chunk of pairs) and truss_gcn_aggregate.h.
+// truss_pairs.h (the set-up of a chunk of pairs), truss_gcn_aggregate.h and truss_gcn_level_agg.h (a level's neighbour sums
+// through the node table).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -516,3 +517,4 @@ extern "C" int truss_debug_stamps(unsigned long long *out16) {
 #include "truss_archive.h"
 #include "truss_pairs.h"
 #include "truss_gcn_aggregate.h"
+#include "truss_gcn_level_agg.h"

@@ -42,7 +42,8 @@
   X(gcn_layer_fused, truss_gcn_layer_fused, false)               \
   X(gcn_layer_terms, truss_gcn_layer_terms, false)               \
   X(gcn_layer_group, truss_gcn_layer_group, false)               \
-  X(pair_setup, truss_pair_setup, false)
+  X(pair_setup, truss_pair_setup, false)                         \
+  X(gcn_level_aggregate, truss_gcn_level_aggregate, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -460,6 +461,41 @@ void gcn_level_backward(int64_t lib, int64_t stream, at::TensorList adj, at::Ten
   check_rc(b, b.gcn_level_backward(args.data(), (int32_t)L, bw.data(), (void *)stream), "truss_gcn_level_backward");
 }
 
+// the neighbour sums of a level through the node table, every item one slice of one launch: y[i] = adj[i] x[i], or adj[i]^T x[i]
+// with transpose[i], over the entries of nbr[i] [N, Kn] only; x[i] / y[i] [B, N, n_ch] (or [B N, n_ch]) contiguous, adj[i] [N, N]
+// (one for the batch) or [B, N, N] == truss_gcn_level_aggregate
+void gcn_level_aggregate(int64_t lib, int64_t stream, at::TensorList x, at::TensorList adj, at::TensorList nbr, at::TensorList y,
+                         const c10::List<bool> &transpose) {
+  const Backend &b = backend(lib);
+  need(b.gcn_level_aggregate, "truss_gcn_level_aggregate");
+  const size_t L = x.size();
+  TORCH_CHECK(adj.size() == L && nbr.size() == L && y.size() == L && transpose.size() == L,
+              "truss_mi355: gcn_level_aggregate takes one entry per item in every list");
+  std::vector<truss_gcn_agg_t> items(L);
+  for (size_t i = 0; i < L; ++i) {
+    TORCH_CHECK(nbr[i].dim() == 2 && (x[i].dim() == 2 || x[i].dim() == 3) && x[i].sizes() == y[i].sizes(),
+                "truss_mi355: gcn_level_aggregate: x / y [B, N, n_ch] of equal shape, nbr [N, Kn]");
+    const int64_t N = nbr[i].size(0), C = x[i].size(-1), rows = x[i].numel() / (C > 0 ? C : 1);
+    TORCH_CHECK(N >= 1 && C >= 1 && rows % N == 0 && (x[i].dim() == 2 || x[i].size(1) == N), "truss_mi355: gcn_level_aggregate: rows of x are not whole graphs of nbr's N nodes");
+    const int64_t B = rows / N;
+    TORCH_CHECK(B <= INT32_MAX && N <= INT32_MAX && C <= INT32_MAX && nbr[i].size(1) <= INT32_MAX, "truss_mi355: gcn_level_aggregate: sizes beyond int32");
+    const bool shared = adj[i].dim() == 2;
+    TORCH_CHECK((shared || adj[i].dim() == 3) && adj[i].size(-1) == N && adj[i].size(-2) == N && (shared || adj[i].size(0) == B),
+                "truss_mi355: gcn_level_aggregate: adj must be [N, N] or [B, N, N]");
+    truss_gcn_agg_t &a = items[i];
+    a = truss_gcn_agg_t{};
+    a.struct_size = sizeof(truss_gcn_agg_t);
+    a.x = ptr<const float>(b, x[i], at::kFloat, "x");
+    a.adj = ptr<const float>(b, adj[i], at::kFloat, "adj");
+    a.a_batch_stride = shared ? 0 : N * N;
+    a.nbr = ptr<const int16_t>(b, nbr[i], at::kShort, "nbr");
+    a.y = ptr<float>(b, y[i], at::kFloat, "y");
+    a.n_batch = (int32_t)B, a.n_nodes = (int32_t)N, a.n_ch = (int32_t)C, a.k_nbr = (int32_t)nbr[i].size(1);
+    a.transpose = transpose.get(i) ? 1 : 0;
+  }
+  check_rc(b, b.gcn_level_aggregate(items.data(), (int32_t)L, (void *)stream), "truss_gcn_level_aggregate");
+}
+
 // w [C, K] float32 -> out [3, 224, KP] int16 (bfloat16 bit patterns, zero rows / columns beyond C / K): the exact three-term split of the bf16x3 path == truss_gcn_split_w
 void gcn_split_w(int64_t lib, int64_t stream, const at::Tensor &w, const at::Tensor &out) {
   const Backend &b = backend(lib);
@@ -829,6 +865,7 @@ TORCH_LIBRARY(truss_mi355, m) {
         "Tensor(c!) par_params, Tensor(d!) par_y, Tensor(e!) par_sec, Tensor(f!) cand_x, Tensor(g!) cand_target, Tensor(h!) cand_params, "
         "Tensor(i!) cand_y, Tensor(j!) cand_sec, Tensor(k!) p0, Tensor(l!) nn0, Tensor(m!) parent_obj, Tensor(n!) ref, Tensor(o!) x_p, "
         "Tensor(p!) A_p, Tensor(q!)? coin) -> ()");
+  m.def("gcn_level_aggregate(int lib, int stream, Tensor[] x, Tensor[] adj, Tensor[] nbr, Tensor(a!)[] y, bool[] transpose) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

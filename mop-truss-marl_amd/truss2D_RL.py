@@ -21,6 +21,7 @@ Multi-GPU: pass `dist=torch.distributed` (backend "nccl" = RCCL on MI355X): ever
 preceded by ONE all-reduce of the flat gradient buffer; the env batch itself needs
 no collective.
 """
+import contextlib
 import random
 from collections import deque
 
@@ -173,12 +174,122 @@ def set_level_backward(fn, device_type="cuda"):
         _LEVEL_BACKWARD[device_type] = fn
 
 
-class _Group:
-    """equally shaped layers of a level: requests `idx`, activation, stacked adjacencies [n B, N, N]"""
-    __slots__ = ("idx", "act", "a", "adjs", "shape")
+# The fused level kernels own whole graphs in a 128-row tile, their dense adjacency included: that envelope ends at 64 nodes
+# (csrc/truss_gcn_level.h, truss_gcn_level_bwd.h).  Above it a level falls to the batched library GEMMs below, which treat the
+# adjacency as a dense N x N matrix although a truss node has at most 9 neighbours -- unless a node table is current
+# (`node_pattern`): then the two N x N products of a group of node-graph layers become sums over the table's entries.
+LEVEL_DENSE_MAX_NODES = 64
 
-    def __init__(self, idx, act, a, adjs, shape):
-        self.idx, self.act, self.a, self.adjs, self.shape = idx, act, a, adjs, shape
+
+class NodePattern:
+    """The sparsity pattern of every node-graph adjacency of one truss as a table: int16 [N, k <= 16], row i lists the columns that
+    may be non-zero in row i, -1 = no entry (TrussTopology.neighbor_table()).  Built from the HOST table (numpy array or CPU tensor)
+    and validated there, once: entries in -1 .. N - 1, no column twice in a row, structurally symmetric (j in row i iff i in row
+    j -- what makes the transposed sum over the same table A^T x); anything else raises ValueError.  `to(device)` uploads it."""
+
+    def __init__(self, table):
+        t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+        if t.dtype != np.int16 or t.ndim != 2 or t.shape[0] < 1 or not 1 <= t.shape[1] <= 16:
+            raise ValueError(f"NodePattern: the table must be int16 [N, k] with 1 <= k <= 16, got {t.dtype} {tuple(t.shape)}")
+        N = t.shape[0]
+        if t.min() < -1 or t.max() >= N:
+            raise ValueError(f"NodePattern: entries must lie in -1 .. {N - 1}")
+        listed = np.zeros((N, N), dtype=np.int32)
+        rows, cols = np.nonzero(t >= 0)
+        np.add.at(listed, (rows, t[rows, cols].astype(np.int64)), 1)
+        if listed.max() > 1:
+            raise ValueError("NodePattern: a column is listed twice in one row")
+        if not np.array_equal(listed, listed.T):
+            raise ValueError("NodePattern: the table is not structurally symmetric (j in row i iff i in row j)")
+        self.n_nodes, self.k = N, t.shape[1]
+        self.table = torch.from_numpy(np.ascontiguousarray(t))
+        self._on = {}
+
+    def to(self, device):
+        self.on(device)
+        return self
+
+    def on(self, device):
+        """the table on `device` (uploaded once; the tensor stays with this object, so a captured graph's address stays valid)"""
+        key = str(torch.device(device))
+        hit = self._on.get(key)
+        if hit is None:
+            hit = self._on[key] = self.table.to(device)
+        return hit
+
+    def gather_index(self, device):
+        """(columns [N, k] int64 with -1 replaced by the row's own index, listed [N, k] bool, rows [N, 1] int64) on `device`"""
+        key = "index " + str(torch.device(device))
+        hit = self._on.get(key)
+        if hit is None:
+            t = self.on(device).long()
+            rows = torch.arange(self.n_nodes, device=t.device)[:, None]
+            hit = self._on[key] = (torch.where(t >= 0, t, rows), t >= 0, rows)
+        return hit
+
+
+_PATTERN = [None]          # the current NodePattern (node_pattern)
+
+
+@contextlib.contextmanager
+def node_pattern(pattern):
+    """Make `pattern` (a NodePattern, or None for none) the current node table: inside, `gcn_level` evaluates every group of layers
+    over graphs of the table's N > LEVEL_DENSE_MAX_NODES nodes through it.  The adjacencies must be zero outside the table."""
+    prev, _PATTERN[0] = _PATTERN[0], pattern
+    try:
+        yield pattern
+    finally:
+        _PATTERN[0] = prev
+
+
+_LEVEL_AGGREGATE = {}      # device type -> callable(groups, xs, transpose) -> [y_g [n, B N, K]] or None (truss_mi355.gcn.level_aggregate)
+
+
+def set_level_aggregate(fn, device_type="cuda"):
+    """Install (or, with None, remove) the neighbour sums of pattern groups for tensors of `device_type`: fn(groups, xs, transpose)
+    with the pattern groups of a level, xs[g] the n tensors [B, N, K] (or [B N, K]) of group g in the order of g.idx, and
+    transpose False (A x) or True (A^T x); it returns one stacked tensor [n, B N, K] per group, or None to leave the sums to the
+    gather-and-sum of `_aggregate_library`."""
+    if fn is None:
+        _LEVEL_AGGREGATE.pop(device_type, None)
+    else:
+        _LEVEL_AGGREGATE[device_type] = fn
+
+
+def _aggregate_library(groups, xs, transpose):
+    """A x (or A^T x) over the table's entries as a gather and a sum: any device, any dtype"""
+    ys = []
+    for g, xg in zip(groups, xs):
+        B, N, K = g.shape
+        cols, listed, rows = g.pattern.gather_index(xg[0].device)
+        y = []
+        for adj, x in zip(g.adjs, xg):
+            coef = adj[:, cols, rows] if transpose else adj[:, rows, cols]                        # [B or 1, N, k]
+            coef = torch.where(listed, coef, torch.zeros((), dtype=coef.dtype, device=coef.device))
+            y.append((coef.unsqueeze(-1) * x.reshape(B, N, K)[:, cols]).sum(dim=2).reshape(B * N, K))
+        ys.append(torch.stack(y))
+    return ys
+
+
+def _aggregate(groups, xs, transpose):
+    fn = _LEVEL_AGGREGATE.get(xs[0][0].device.type)
+    res = fn(groups, xs, transpose) if fn is not None else None
+    return res if res is not None else _aggregate_library(groups, xs, transpose)
+
+
+class _Group:
+    """equally shaped layers of a level: requests `idx`, activation, stacked adjacencies `a` [n B, N, N] -- built when the library
+    path first asks for them (a = None), never for a group with a `pattern`"""
+    __slots__ = ("idx", "act", "_a", "adjs", "shape", "cache", "pattern")
+
+    def __init__(self, idx, act, a, adjs, shape, cache=None, pattern=None):
+        self.idx, self.act, self._a, self.adjs, self.shape, self.cache, self.pattern = idx, act, a, adjs, shape, cache, pattern
+
+    @property
+    def a(self):
+        if self._a is None:
+            self._a = _adj_stack(self.adjs, self.shape[0], self.shape[1], self.cache)
+        return self._a
 
 
 def _adj_stack(adjs, B, N, cache=None):
@@ -202,14 +313,18 @@ class _GcnLevel(torch.autograd.Function):
         L = len(tensors) // 3
         xs, ws, bs = tensors[:L], tensors[L:2 * L], tensors[2 * L:]
         outs = xaggs = None
+        # groups that carry a pattern sum their neighbours through the table (below); the others go to the fused forward, where one
+        # is installed, or to the library.  No pattern group: `dense` IS `groups`, the level runs as it always has.
+        table = [g for g in groups if g.pattern is not None]
+        dense = [g for g in groups if g.pattern is None] if table else groups
         fused = _LEVEL_FORWARD.get(xs[0].device.type)
-        if fused is not None:
-            res = fused(groups, xs, ws, bs, want_grad)
+        if fused is not None and dense:
+            res = fused(dense, xs, ws, bs, want_grad)
             if res is not None:
                 outs, xaggs = res
         if outs is None:
             outs, xaggs = [], []
-            for g in groups:
+            for g in dense:
                 n, (B, N, K), C = len(g.idx), g.shape, ws[g.idx[0]].shape[0]
                 x0 = xs[g.idx[0]]
                 xst = x0.expand(n, B, N, K) if all(xs[i] is x0 for i in g.idx) else torch.stack([xs[i] for i in g.idx])
@@ -220,6 +335,18 @@ class _GcnLevel(torch.autograd.Function):
                 o = torch.relu_(o) if g.act == "relu" else torch.sigmoid_(o) if g.act == "sigmoid" else o
                 outs.append(o.view(n, B, N, C))
                 xaggs.append(xa)
+        if table:
+            t_xa = _aggregate(table, [[xs[i] for i in g.idx] for g in table], False)               # X' = A X, over the table
+            t_out = []
+            for g, xa in zip(table, t_xa):
+                n, (B, N, K), C = len(g.idx), g.shape, ws[g.idx[0]].shape[0]
+                wst = torch.stack([ws[i] for i in g.idx])
+                bst = torch.stack([bs[i] for i in g.idx])[:, None, :]
+                o = torch.baddbmm(bst, xa, wst.transpose(1, 2))
+                o = torch.relu_(o) if g.act == "relu" else torch.sigmoid_(o) if g.act == "sigmoid" else o
+                t_out.append(o.view(n, B, N, C))
+            by_group = {id(g): pair for gs, pairs in ((dense, zip(outs, xaggs)), (table, zip(t_out, t_xa))) for g, pair in zip(gs, pairs)}
+            outs, xaggs = [by_group[id(g)][0] for g in groups], [by_group[id(g)][1] for g in groups]      # request order
         ctx.groups, ctx.L = groups, L
         ctx.set_materialize_grads(False)       # a group nothing flows back into arrives as None in backward, not as a tensor of zeros
         if want_grad:
@@ -244,14 +371,49 @@ class _GcnLevel(torch.autograd.Function):
         # needs_input_grad of apply((plan), *xs, *ws, *bs) -- need[1 + i], need[1 + L + i], need[1 + 2 L + i] for x, w, b of request i.
         # It returns (dx, dw, db), lists of length L in request order (None where nothing is needed; the pieces of a group are the
         # `unbind` of ONE stacked tensor per quantity), or None to leave the whole level to the library path below.
+        # Groups that carry a pattern are differentiated here (at the end); the others are what the fused backward, or the library
+        # path, is handed -- all of them where no group carries a pattern, in the very lists that arrived.
+        table = [gi for gi, g in enumerate(groups) if g.pattern is not None]
+        dense = [gi for gi, g in enumerate(groups) if g.pattern is None] if table else range(G)
         fused = _LEVEL_BACKWARD.get(outs[0].device.type) if G else None
-        if fused is not None:
-            res = fused(groups, douts, outs, xaggs, ws, need)
+        dx = None
+        if fused is not None and (dense or not table):
+            sub = (lambda seq: [seq[gi] for gi in dense]) if table else (lambda seq: seq)
+            res = fused(sub(groups), sub(douts), sub(outs), sub(xaggs), ws, need)
             if res is not None:
                 dx, dw, db = res
-                return (None, *dx, *dw, *db)
-        dx, dw, db = [None] * L, [None] * L, [None] * L
-        for gi, g in enumerate(groups):
+                if not table:
+                    return (None, *dx, *dw, *db)
+                dx, dw, db = list(dx), list(dw), list(db)
+        if dx is None:
+            dx, dw, db = [None] * L, [None] * L, [None] * L
+            for gi in dense:
+                g = groups[gi]
+                need_w = any(need[1 + L + i] or need[1 + 2 * L + i] for i in g.idx)
+                need_x = any(need[1 + i] for i in g.idx)
+                if douts[gi] is None or not (need_w or need_x):
+                    continue
+                n, (B, N, K) = len(g.idx), g.shape
+                o = outs[gi]
+                C = o.shape[-1]
+                d = douts[gi].contiguous()
+                dz = (torch.ops.aten.threshold_backward(d, o, 0.0) if g.act == "relu" else
+                      torch.ops.aten.sigmoid_backward(d, o) if g.act == "sigmoid" else d).view(n, B * N, C)
+                if need_w:
+                    for i, piece in zip(g.idx, torch.bmm(dz.transpose(1, 2), xaggs[gi]).unbind(0)):     # dW = dZ^T X'   [n, C, K]
+                        dw[i] = piece
+                    for i, piece in zip(g.idx, dz.sum(dim=1).unbind(0)):
+                        db[i] = piece
+                if need_x:
+                    gw = torch.bmm(dz, torch.stack([ws[i] for i in g.idx]))                             # dZ W           [n, B N, K]
+                    gx = torch.bmm(g.a.transpose(1, 2), gw.view(n * B, N, K)).view(n, B, N, K)         # A^T (dZ W)
+                    for i, piece in zip(g.idx, gx.unbind(0)):
+                        dx[i] = piece                          # (one tensor passed for several layers: autograd adds per argument)
+        # pattern groups: dZ, db, dW as above; dX = A^T (dZ W) over the table (symmetric: the same table serves A^T), all groups of the
+        # level in one call of the aggregation
+        back, gws = [], []
+        for gi in table:
+            g = groups[gi]
             need_w = any(need[1 + L + i] or need[1 + 2 * L + i] for i in g.idx)
             need_x = any(need[1 + i] for i in g.idx)
             if douts[gi] is None or not (need_w or need_x):
@@ -263,30 +425,38 @@ class _GcnLevel(torch.autograd.Function):
             dz = (torch.ops.aten.threshold_backward(d, o, 0.0) if g.act == "relu" else
                   torch.ops.aten.sigmoid_backward(d, o) if g.act == "sigmoid" else d).view(n, B * N, C)
             if need_w:
-                for i, piece in zip(g.idx, torch.bmm(dz.transpose(1, 2), xaggs[gi]).unbind(0)):     # dW = dZ^T X'   [n, C, K]
+                for i, piece in zip(g.idx, torch.bmm(dz.transpose(1, 2), xaggs[gi]).unbind(0)):
                     dw[i] = piece
                 for i, piece in zip(g.idx, dz.sum(dim=1).unbind(0)):
                     db[i] = piece
             if need_x:
-                gw = torch.bmm(dz, torch.stack([ws[i] for i in g.idx]))                             # dZ W           [n, B N, K]
-                gx = torch.bmm(g.a.transpose(1, 2), gw.view(n * B, N, K)).view(n, B, N, K)         # A^T (dZ W)
-                for i, piece in zip(g.idx, gx.unbind(0)):
-                    dx[i] = piece                          # (one tensor passed for several layers: autograd adds per argument)
+                back.append(g)
+                gws.append(list(torch.bmm(dz, torch.stack([ws[i] for i in g.idx])).unbind(0)))          # dZ W, per layer [B N, K]
+        if back:
+            for g, gx in zip(back, _aggregate(back, gws, True)):
+                for i, piece in zip(g.idx, gx.view(len(g.idx), *g.shape).unbind(0)):
+                    dx[i] = piece
         return (None, *dx, *dw, *db)
 
 
 def gcn_level(reqs, cache=None):
     """reqs: [(GCNConv layer, x [B,N,K], adjacency [B,N,N] or [1,N,N], activation)] -> [act(adj @ x @ W^T + b)] in request order.
-    Layers of equal shapes and activation form a group (one set of batched GEMMs forward and backward)."""
+    Layers of equal shapes and activation form a group (one set of batched GEMMs forward and backward).  Inside `node_pattern(p)` the
+    groups over graphs of p's N > LEVEL_DENSE_MAX_NODES nodes sum their neighbours through p's table instead of a dense N x N product
+    (forward X' = A X and backward dX = A^T (dZ W)); their adjacencies must be zero outside the table."""
     by_key = {}
     live = torch.is_grad_enabled()
     for i, (layer, x, adj, act) in enumerate(reqs):
         trains = live and (x.requires_grad or layer.lin.weight.requires_grad)      # frozen passes evaluated alongside: groups of their own
         by_key.setdefault((tuple(x.shape), layer.lin.out_features, act, trains), []).append(i)
     groups = []
+    pattern = _PATTERN[0]
     for (shape, _, act, _), idx in by_key.items():
         adjs = [reqs[i][2] for i in idx]
-        groups.append(_Group(idx, act, _adj_stack(adjs, shape[0], shape[1], cache), adjs, shape))
+        # the node-graph layers of a truss beyond the level kernels' dense envelope take the current table (the Pareto graph,
+        # P <= 64 members, and every smaller truss stay on the dense paths); the dense stack is built when first asked for
+        table = pattern if pattern is not None and shape[1] == pattern.n_nodes and shape[1] > LEVEL_DENSE_MAX_NODES else None
+        groups.append(_Group(idx, act, None, adjs, shape, cache, table))
     tensors = [r[1] for r in reqs] + [r[0].lin.weight for r in reqs] + [r[0].bias for r in reqs]
     want_grad = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
     outs = _GcnLevel.apply((groups, want_grad), *tensors)

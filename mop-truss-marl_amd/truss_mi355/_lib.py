@@ -136,6 +136,7 @@ _LATER_ENTRIES = [
     ("truss_gcn_layer_terms", [_vp, _vp, _i32, _vp]),
     ("truss_gcn_layer_group", [_vp, _vp, _i32, _i32, _i32, _vp]),
     ("truss_pair_setup", [C.POINTER(PairArgs), _vp]),
+    ("truss_gcn_level_aggregate", [_vp, _i32, _vp]),
 ]
 
 
@@ -173,6 +174,7 @@ class TrussLib:
         self.has_gcn_terms = "truss_gcn_layer_terms" in found                                # the split-weight layer on one or two bf16 terms
         self.has_gcn_group = "truss_gcn_layer_group" in found                                # several split-weight layers in one launch
         self.has_pair_setup = "truss_pair_setup" in found                                    # the fused set-up of a chunk of pairs
+        self.has_level_aggregate = "truss_gcn_level_aggregate" in found                      # a level's neighbour sums through the node table
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")
         self.backend = d.truss_backend().decode()

@@ -1,7 +1,7 @@
 """Host glue of the GCN kernels (csrc/truss_gcn*.h) and the inference of the actors on them.
 
     one layer                gcn_layer / gcn_layer_head / gcn_layer_pool / gcn_layer_group, gcn_aggregate; split_weights
-    one level of the update  level_forward / level_backward (the hooks truss2D_RL._GcnLevel calls)
+    one level of the update  level_forward / level_backward / level_aggregate (the hooks truss2D_RL._GcnLevel calls)
     an actor, three actors   actor_infer / actors_infer, which both read ONE statement of the network (`_ACTOR_*`)
 """
 from __future__ import annotations
@@ -291,6 +291,32 @@ def level_backward(lib):
                     dx[i] = piece                          # (one tensor passed for several layers: autograd adds per argument)
         ops.call(ops.namespace().gcn_level_backward, ops.bind(lib), ops.stream_of(OUT[0].device), ADJ, W, ACT, DOUT, OUT, XAGG, DW, DB, DX)
         return dx, dw, db
+    return run
+
+
+def level_aggregate(lib):
+    """The neighbour sums of the pattern groups of a level (`truss_gcn_level_aggregate`, csrc/truss_gcn_level_agg.h: ONE call for every
+    layer of every group of a level and direction) in the shape truss2D_RL._aggregate asks for: callable(groups, xs, transpose) ->
+    [y_g [n, B N, K]], one stacked tensor per group whose slices the launch writes, or None for anything but float32 (the caller
+    then gathers and sums with framework operators).  Installed by BatchedMARL(level_adjacency="table") on the GPU
+    (`truss2D_RL.set_level_aggregate`)."""
+
+    def run(groups, xs, transpose):
+        X, ADJ, NBR, Y, ys = [], [], [], [], []
+        for g, xg in zip(groups, xs):
+            n, (B, N, K), dev = len(g.idx), g.shape, xg[0].device
+            if any(x.dtype != torch.float32 for x in xg) or any(a.dtype != torch.float32 for a in g.adjs):
+                return None
+            nbr = g.pattern.on(dev)
+            y = torch.empty((n, B * N, K), dtype=torch.float32, device=dev)
+            for j, x in enumerate(xg):
+                X.append(x.detach().contiguous())
+                ADJ.append(_adj(g.adjs[j], expanded=True))
+                NBR.append(nbr)
+                Y.append(y[j].view(x.shape))                # (x is [B, N, K] forward, [B N, K] backward: the operator wants equal shapes)
+            ys.append(y)
+        ops.call(ops.namespace().gcn_level_aggregate, ops.bind(lib), ops.stream_of(X[0].device), X, ADJ, NBR, Y, [bool(transpose)] * len(X))
+        return ys
     return run
 
 

@@ -56,7 +56,7 @@ from . import _lib
 from . import reward as RW
 from .batched import BatchedTruss
 from .gcn import (PRECISIONS, actor_infer, actors_infer, gcn_aggregate, gcn_layer, gcn_layer_group, gcn_layer_head, gcn_layer_pool,  # noqa: F401
-                  level_backward, level_forward, refresh_actor_caches, split_weights)
+                  level_aggregate, level_backward, level_forward, refresh_actor_caches, split_weights)
 from .pairs import design_coins, pair_dtab, pair_frac_tab, pair_setup, pareto_graph, path_graph_table  # noqa: F401
 from .replay import DeviceReplay
 from .topology import TrussTopology
@@ -139,14 +139,19 @@ class BatchedMARL:
     level_backward: how the update differentiates a level of GCN layers on the GPU -- "library" (batched library GEMMs, the
     default) or "hip" (one `truss_gcn_level_backward` launch per level); None: "hip" if the environment has
     TRUSS_LEVEL_BACKWARD=1, else "library".  The choice is installed process-wide for cuda tensors (like the level forward)
-    and is part of an update graph from the moment it is captured."""
+    and is part of an update graph from the moment it is captured.
+    level_adjacency: how the update's levels apply the node-graph adjacencies of a truss of MORE than 64 nodes (up to 64 the fused
+    level kernels own whole graphs and this option changes nothing) -- "dense" (batched library GEMMs over stacked N x N
+    adjacencies, the default) or "table" (sums over the entries of `topo.neighbor_table()`, one `truss_gcn_level_aggregate` launch
+    per level and direction on the GPU; needs a library with that entry; the sampled adjacencies are zero outside the table by
+    construction); None: "table" if the environment has TRUSS_LEVEL_ADJACENCY=table, else "dense"."""
 
     def __init__(self, topo: TrussTopology, n_envs: int, maddpg, *, max_front: int | None = None, lib=None, device=None,
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
                  pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None,
                  level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None,
                  archive_path: str | None = None, actor_path: str | None = None, actor_precision: str | None = None,
-                 pair_path: str | None = None):
+                 pair_path: str | None = None, level_adjacency: str | None = None):
         if game not in ("train", "test"):
             raise ValueError(f"game must be 'train' or 'test', got {game!r}")
         if game == "test" and len(topo.sym_nodes) == 0:
@@ -175,13 +180,21 @@ class BatchedMARL:
         if self.device.type == "cuda" and os.environ.get("TRUSS_LEVEL_FORWARD", "1") != "0":
             import truss2D_RL
             truss2D_RL.set_level_forward(level_forward(self.lib), "cuda")   # the update's forward passes: one launch per level
-        self._options(level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision)
+        self._options(level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision, level_adjacency)
         self._arch_spare = None       # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
         self._pair_dtab = self._pair_frac = None   # pair_path="hip": deg^-1/2 and n / P as the framework rounds them on this device
         #                                             (pair_dtab, pair_frac_tab; made at the first step)
         if self.device.type == "cuda":
             import truss2D_RL
             truss2D_RL.set_level_backward(_level_backward_hook(self.lib) if self.level_backward == "hip" else None, "cuda")
+        # level_adjacency="table": the node table of this truss, current during every update of this engine (`_train`); the table's
+        # device tensor stays with the pattern, i.e. with the engine: a captured update holds its address
+        self.pattern = None
+        if self.level_adjacency == "table":
+            import truss2D_RL
+            self.pattern = truss2D_RL.NodePattern(topo.neighbor_table()).to(self.device)
+            if self.device.type == "cuda":
+                truss2D_RL.set_level_aggregate(level_aggregate(self.lib), "cuda")
         dev, B, P, N, E = self.device, self.B, self.P, topo.N, topo.E
         A_n, mask = topo.normalized_adjacency()
         self.A_n = torch.tensor(A_n, device=dev)[None]
@@ -209,13 +222,16 @@ class BatchedMARL:
         self._tg, self.use_train_graph = None, True
         self.profile = None            # set to {} to accumulate synchronised wall time per segment (diagnostic)
 
-    def _options(self, level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision):
+    def _options(self, level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision, level_adjacency):
         # (see the class) argument, else environment, else default; then what the choice needs of the library and of max_front
         def lib_has(flag, what, entry):
             if not flag:
                 raise ValueError(f"{what}: {self.lib.path} has no {entry}")
 
         self.level_backward = _option("level_backward", level_backward, "TRUSS_LEVEL_BACKWARD", ("library", "hip"), {"1": "hip"})
+        self.level_adjacency = _option("level_adjacency", level_adjacency, "TRUSS_LEVEL_ADJACENCY", ("dense", "table"))
+        if self.level_adjacency == "table":
+            lib_has(self.lib.has_level_aggregate, "level_adjacency='table'", "truss_gcn_level_aggregate")
         self.replay_storage = _option("replay_storage", replay_storage, "TRUSS_REPLAY_STORAGE", ("dense", "compact"))
         self.reward_path = _option("reward_path", reward_path, "TRUSS_REWARD", ("torch", "hip"))
         if self.reward_path == "hip":
@@ -334,6 +350,14 @@ class BatchedMARL:
 
     # ---- the MADDPG update: eager, or (one GPU) replayed as a hipGraph ----
     def _train(self, S, NS, A, R):
+        """`_update` with this engine's node table current (level_adjacency="table"): the eager updates, the warm-up, the capture"""
+        if self.pattern is None:
+            return self._update(S, NS, A, R)
+        import truss2D_RL
+        with truss2D_RL.node_pattern(self.pattern):
+            return self._update(S, NS, A, R)
+
+    def _update(self, S, NS, A, R):
         """The update is thousands of small kernels at batch 32 -- launch-bound.  On the GPU it is captured once into a hipGraph
         (static input buffers, capturable Adam) and replayed -- data-parallel too: the gradient all-reduces (RCCL; one flat
         buffer for the three critics, one per actor) are captured WITH the update, every rank replaying its own copy of the same
