@@ -686,6 +686,59 @@ int truss_replay_scatter(const truss_replay_field_t *fields, int32_t n_fields, c
 int truss_replay_gather(const truss_replay_field_t *fields, int32_t n_fields, const int64_t *idx, int32_t batch, int64_t capacity,
                         void *stream);
 
+/* ---- optimiser step: per-tensor gradient clip and Adam over a list of parameter tensors, two launches ------------------
+ * replaces: the critic's Adam and the fresh Adam every actor update builds, both with clipnorm=1 (truss2D_RL.py:629/658/688 and the
+ * critic optimisers created with the agents): Keras clips every gradient tensor to L2 norm <= 1 on its own, then applies Adam.
+ * One call is one optimiser step over n_tensors parameter tensors whose gradients, and moments, lie in FLAT float32 vectors:
+ * tensor i owns the elements [offset, offset + numel) of grad / exp_avg / exp_avg_sq / clipped and the numel contiguous floats at p.
+ * Per tensor, with g its slice of grad (u = 2^-24 roundings as written, nothing contracted, correctly rounded / and sqrt):
+ *   s = sum g_j^2 in float64 (a float32 square is exact there), norm = (float) sqrt(s), fac = min(1.0f, 1.0f / (norm + 1e-12f)),
+ *   c_j = g_j * fac                                                                                        -- then, all float32,
+ *   TRUSS_OPTIM_ADAM        m' = m + (1 - beta1) (c - m);  v' = v beta2 + ((1 - beta2) c) c;
+ *                           den = sqrtf(v') / (float) sqrt(1 - beta2^t) + eps;  w' = w + ((1 / den) m') (float)(-lr / (1 - beta1^t))
+ *                           with beta^t in float64 from t = *step, the step number (>= 1) the CALLER has already incremented: the
+ *                           kernels only read it;
+ *   TRUSS_OPTIM_FIRST_STEP  w' = w + (float)(-lr) (c / (|c| + eps)): step 1 of an Adam with zero moments; exp_avg, exp_avg_sq
+ *                           and step are not read (NULL).
+ * Two launches per TRUSS_OPTIM_MAX_TENSORS tensors (longer lists run as consecutive pairs), one 256-thread workgroup per chunk of
+ * TRUSS_OPTIM_CHUNK elements of a tensor in both: the first writes every chunk's float64 sum of squares to partials[chunk], the
+ * second adds its tensor's partials in chunk order, forms fac and updates its chunk.  16-byte accesses where every address of the
+ * chunk allows and its length is a multiple of 4, word by word otherwise (the sums do not depend on which).  The descriptors travel in the kernel arguments: the entry
+ * allocates nothing and does not synchronise; capturable.  Every output element has one owner and every sum a fixed order (no
+ * atomics): two calls on equal inputs give equal bits.
+ *   tensors   HOST array [n_tensors]: p device pointer (contiguous), numel 1..2^31-1, ranges ascending and disjoint
+ *   grad      device, read only       exp_avg, exp_avg_sq  device, updated in place (ADAM)       step  device double (ADAM)
+ *   partials  device scratch of sum_i ceil(numel_i / TRUSS_OPTIM_CHUNK) doubles, the caller's
+ *   clipped   NULL, or flat float32 like grad: c as the kernel used it, the tensors' ranges only    norms  NULL, or float32 [n_tensors]
+ * TRUSS_EINVAL, with nothing launched or written: bad struct_size, unknown mode, n_tensors < 0, a NULL tensors / grad / partials /
+ * p, exp_avg / exp_avg_sq / step missing in ADAM mode, numel outside 1..2^31-1, ranges not ascending and disjoint, lr / eps / betas
+ * not finite or betas outside [0, 1), an output (p, exp_avg, exp_avg_sq, clipped, norms, partials) overlapping the tensors' span
+ * of grad.  n_tensors == 0: TRUSS_OK, no launch.  Optional entry of ABI version 3 (a library may lack it). */
+#define TRUSS_OPTIM_ADAM 0
+#define TRUSS_OPTIM_FIRST_STEP 1
+#define TRUSS_OPTIM_CHUNK 4096         /* elements per workgroup */
+#define TRUSS_OPTIM_MAX_TENSORS 160    /* tensors per launch pair */
+typedef struct truss_optim_tensor {
+  float *p;
+  int64_t offset;
+  int64_t numel;
+} truss_optim_tensor_t;
+typedef struct truss_optim_args {
+  size_t struct_size;
+  int32_t mode;
+  int32_t n_tensors;
+  const truss_optim_tensor_t *tensors;
+  const float *grad;
+  float *exp_avg;
+  float *exp_avg_sq;
+  const double *step;
+  double lr, beta1, beta2, eps;
+  double *partials;
+  float *clipped;
+  float *norms;
+} truss_optim_args_t;
+int truss_optim_step(const truss_optim_args_t *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

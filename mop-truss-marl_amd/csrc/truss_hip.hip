@@ -10,7 +10,7 @@
 // header of its own, included at the end: truss_gcn.h, truss_gcn_level.h, truss_gcn_level_bwd.h, truss_replay.h, truss_front.h
 // (Pareto front + hypervolume), truss_reward.h (the difference reward), truss_archive.h (the archive update),
 // truss_pairs.h (the set-up of a chunk of pairs), truss_gcn_aggregate.h and truss_gcn_level_agg.h (a level's neighbour sums
-// through the node table).
+// through the node table), truss_optim.h (clip and Adam of the MADDPG update).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -518,3 +518,4 @@ extern "C" int truss_debug_stamps(unsigned long long *out16) {
 #include "truss_pairs.h"
 #include "truss_gcn_aggregate.h"
 #include "truss_gcn_level_agg.h"
+#include "truss_optim.h"

@@ -43,7 +43,8 @@
   X(gcn_layer_terms, truss_gcn_layer_terms, false)               \
   X(gcn_layer_group, truss_gcn_layer_group, false)               \
   X(pair_setup, truss_pair_setup, false)                         \
-  X(gcn_level_aggregate, truss_gcn_level_aggregate, false)
+  X(gcn_level_aggregate, truss_gcn_level_aggregate, false)        \
+  X(optim_step, truss_optim_step, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -496,6 +497,48 @@ void gcn_level_aggregate(int64_t lib, int64_t stream, at::TensorList x, at::Tens
   check_rc(b, b.gcn_level_aggregate(items.data(), (int32_t)L, (void *)stream), "truss_gcn_level_aggregate");
 }
 
+// one optimiser step over the list `params` (each contiguous float32, updated in place): the gradient of params[i] is the slice of
+// the flat vector `grad` behind those of params[< i] -- the offsets are the running sum of the sizes -- clipped to L2 norm <= 1 on
+// its own; then Adam on the flat moments exp_avg / exp_avg_sq at step number *step (a float64 tensor the caller has already
+// incremented), or, with mode 1, the first step of a fresh Adam (no moments, no step).  partials: float64 scratch of one element
+// per chunk of TRUSS_OPTIM_CHUNK elements of every tensor; clipped (flat like grad) / norms ([len(params)]): optional outputs
+// == truss_optim_step
+void optim_step(int64_t lib, int64_t stream, int64_t mode, at::TensorList params, const at::Tensor &grad, const OT &exp_avg,
+                const OT &exp_avg_sq, const OT &step, double lr, double beta1, double beta2, double eps, const at::Tensor &partials,
+                const OT &clipped, const OT &norms) {
+  const Backend &b = backend(lib);
+  need(b.optim_step, "truss_optim_step");
+  const size_t L = params.size();
+  TORCH_CHECK(L <= (size_t)INT32_MAX, "truss_mi355: optim_step: too many tensors");
+  std::vector<truss_optim_tensor_t> ts(L);
+  int64_t total = 0, chunks = 0;
+  for (size_t i = 0; i < L; ++i) {
+    ts[i].p = ptr<float>(b, params[i], at::kFloat, "params[i]", 1);
+    ts[i].offset = total;
+    ts[i].numel = params[i].numel();
+    total += ts[i].numel;
+    chunks += (ts[i].numel + TRUSS_OPTIM_CHUNK - 1) / TRUSS_OPTIM_CHUNK;
+  }
+  TORCH_CHECK(grad.numel() == total, "truss_mi355: optim_step: grad has ", grad.numel(), " elements, the parameters ", total);
+  TORCH_CHECK(!present(exp_avg) || exp_avg->numel() == total, "truss_mi355: optim_step: exp_avg must hold ", total, " elements");
+  TORCH_CHECK(!present(exp_avg_sq) || exp_avg_sq->numel() == total, "truss_mi355: optim_step: exp_avg_sq must hold ", total, " elements");
+  TORCH_CHECK(!present(clipped) || clipped->numel() == total, "truss_mi355: optim_step: clipped must hold ", total, " elements");
+  truss_optim_args_t a{};
+  a.struct_size = sizeof(truss_optim_args_t);
+  a.mode = (int32_t)mode;
+  a.n_tensors = (int32_t)L;
+  a.tensors = ts.data();
+  a.grad = ptr<const float>(b, grad, at::kFloat, "grad");
+  a.exp_avg = ptr<float>(b, exp_avg, at::kFloat, "exp_avg");
+  a.exp_avg_sq = ptr<float>(b, exp_avg_sq, at::kFloat, "exp_avg_sq");
+  a.step = ptr<const double>(b, step, at::kDouble, "step", 1);
+  a.lr = lr, a.beta1 = beta1, a.beta2 = beta2, a.eps = eps;
+  a.partials = ptr<double>(b, partials, at::kDouble, "partials", chunks);
+  a.clipped = ptr<float>(b, clipped, at::kFloat, "clipped");
+  a.norms = ptr<float>(b, norms, at::kFloat, "norms", (int64_t)L);
+  check_rc(b, b.optim_step(&a, (void *)stream), "truss_optim_step");
+}
+
 // w [C, K] float32 -> out [3, 224, KP] int16 (bfloat16 bit patterns, zero rows / columns beyond C / K): the exact three-term split of the bf16x3 path == truss_gcn_split_w
 void gcn_split_w(int64_t lib, int64_t stream, const at::Tensor &w, const at::Tensor &out) {
   const Backend &b = backend(lib);
@@ -866,6 +909,8 @@ TORCH_LIBRARY(truss_mi355, m) {
         "Tensor(i!) cand_y, Tensor(j!) cand_sec, Tensor(k!) p0, Tensor(l!) nn0, Tensor(m!) parent_obj, Tensor(n!) ref, Tensor(o!) x_p, "
         "Tensor(p!) A_p, Tensor(q!)? coin) -> ()");
   m.def("gcn_level_aggregate(int lib, int stream, Tensor[] x, Tensor[] adj, Tensor[] nbr, Tensor(a!)[] y, bool[] transpose) -> ()");
+  m.def("optim_step(int lib, int stream, int mode, Tensor(a!)[] params, Tensor grad, Tensor(b!)? exp_avg, Tensor(c!)? exp_avg_sq, Tensor? step, "
+        "float lr, float beta1, float beta2, float eps, Tensor(d!) partials, Tensor(e!)? clipped, Tensor(f!)? norms) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

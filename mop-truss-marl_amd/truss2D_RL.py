@@ -174,6 +174,21 @@ def set_level_backward(fn, device_type="cuda"):
         _LEVEL_BACKWARD[device_type] = fn
 
 
+_OPTIMIZER_STEP = {}       # device type -> callable(params, flat_grad, lr, eps, betas=None, step=None, exp_avg=None, exp_avg_sq=None) (truss_mi355.optim.optimizer_step)
+
+
+def set_optimizer_step(fn, device_type="cuda"):
+    """Install (or, with None, remove) the fused optimiser step of `MADDPG.train_on_batch` for parameters on `device_type`.  One call
+    `fn(params, flat_grad, lr, eps, betas=, step=, exp_avg=, exp_avg_sq=)` takes the place of `_clip_flat` and the Adam arithmetic:
+    it clips every tensor's slice of `flat_grad` (the unclipped gradients of `params` as one vector, which it leaves as it is) to L2
+    norm <= 1 and updates `params` in place -- with `step` (a 0-dim float64 tensor, already incremented) and the flat moments
+    `exp_avg` / `exp_avg_sq` as `SharedStepAdam.step` would, updating the moments in place; with step None as `_fresh_adam_step`."""
+    if fn is None:
+        _OPTIMIZER_STEP.pop(device_type, None)
+    else:
+        _OPTIMIZER_STEP[device_type] = fn
+
+
 # The fused level kernels own whole graphs in a 128-row tile, their dense adjacency included: that envelope ends at 64 nodes
 # (csrc/truss_gcn_level.h, truss_gcn_level_bwd.h).  Above it a level falls to the batched library GEMMs below, which treat the
 # adjacency as a dense N x N matrix although a truss node has at most 9 neighbours -- unless a node table is current
@@ -637,8 +652,10 @@ class SharedStepAdam:
         return [] if self.step_t is None else [self.step_t, self.exp_avg, self.exp_avg_sq]
 
     @torch.no_grad()
-    def step(self, flat_grad=None):
-        """flat_grad: the (clipped) gradient of all parameters as one vector (`_flat_grads`); default: built from p.grad"""
+    def step(self, flat_grad=None, fused=None):
+        """flat_grad: the (clipped) gradient of all parameters as one vector (`_flat_grads`); default: built from p.grad.
+        fused: a hook of `set_optimizer_step`, which then clips (flat_grad is the UNCLIPPED gradient) and does the arithmetic; the
+        step counter and the moments stay this object's"""
         ps = self.params
         if flat_grad is None:
             if any(p.grad is None for p in ps):
@@ -649,6 +666,9 @@ class SharedStepAdam:
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(flat_grad), torch.zeros_like(flat_grad)
         m, v, g = self.exp_avg, self.exp_avg_sq, flat_grad
         self.step_t += 1
+        if fused is not None:            # (`set_optimizer_step`: clip and Adam in one call, from the UNCLIPPED gradient)
+            fused(ps, g, self.lr, self.eps, betas=(self.b1, self.b2), step=self.step_t, exp_avg=m, exp_avg_sq=v)
+            return
         bc1 = 1 - torch.pow(self.b1, self.step_t)
         bc2_sqrt = (1 - torch.pow(self.b2, self.step_t)).sqrt_().float()
         m.lerp_(g, 1 - self.b1)
@@ -873,7 +893,11 @@ class MADDPG:
             ag.c_loss.append(losses[i].detach())     # stays on the device: no synchronisation inside the update
         allp = [p for cp in cps for p in cp]
         flat = _allreduce_flat(_flat_grads(allp), self.dist)         # (p.grad keeps the local, unclipped gradient)
-        self.critics_opt.step(_clip_flat(flat, allp))
+        fused = _OPTIMIZER_STEP.get(flat.device.type)                # (`set_optimizer_step`)
+        if fused is None:
+            self.critics_opt.step(_clip_flat(flat, allp))
+        else:
+            SharedStepAdam.step(self.critics_opt, flat, fused=fused)
         # The actor updates stay one after the other: agent i's loss re-evaluates ALL three actors (:617-629), i.e. it sees the
         # weights agents < i have just stepped to -- one collective per actor.  (The other two actors' passes carry no gradient
         # that is asked for -- autograd.grad is taken with respect to agent i's parameters only -- so they run without a graph.)
@@ -893,8 +917,11 @@ class MADDPG:
             grads = torch.autograd.grad(actor_loss, ap)
             for p, g in zip(ap, grads):
                 p.grad = g
-            flat = _clip_flat(_allreduce_flat(_flat_grads(ap), self.dist), ap)
-            _fresh_adam_step(ap, ag.lr * 0.1, 1e-7, flat)                                # a fresh optimiser every call (:629)
+            flat = _allreduce_flat(_flat_grads(ap), self.dist)
+            if fused is None:
+                _fresh_adam_step(ap, ag.lr * 0.1, 1e-7, _clip_flat(flat, ap))             # a fresh optimiser every call (:629)
+            else:
+                fused(ap, flat, ag.lr * 0.1, 1e-7)
             # agent i's weights have just changed: an evaluation of actor i taken before this step must not be reused (the others'
             # stay valid: agents > i have not stepped yet, evaluations of agents < i were taken after their steps)
             frozen = {j: v for j, v in frozen.items() if j != i}

@@ -98,6 +98,23 @@ class PairArgs(C.Structure):
 PAIR_MAXP = 256           # truss_pair_setup: rows of the archive per env
 
 
+class OptimTensor(C.Structure):
+    _fields_ = [("p", _vp), ("offset", C.c_int64), ("numel", C.c_int64)]
+
+
+class OptimArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_size_t), ("mode", C.c_int32), ("n_tensors", C.c_int32), ("tensors", C.POINTER(OptimTensor)), ("grad", _vp),
+        ("exp_avg", _vp), ("exp_avg_sq", _vp), ("step", _vp), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+        ("eps", C.c_double), ("partials", _vp), ("clipped", _vp), ("norms", _vp),
+    ]
+
+
+OPTIM_ADAM, OPTIM_FIRST_STEP = 0, 1   # truss_optim_step: mode
+OPTIM_CHUNK = 4096                    # ... elements per workgroup: `partials` holds one double per chunk of every tensor
+OPTIM_MAX_TENSORS = 160               # ... tensors per launch pair
+
+
 _i32, _i64 = C.c_int32, C.c_int64
 _STRING_GETTERS = ("truss_last_error", "truss_backend")       # return const char *; every other entry returns int
 # THE table of the C ABI (with _LATER_ENTRIES below, which see): (symbol, argtypes, optional).  A library may lack the optional entries (the CPU lane emulator does);
@@ -137,6 +154,7 @@ _LATER_ENTRIES = [
     ("truss_gcn_layer_group", [_vp, _vp, _i32, _i32, _i32, _vp]),
     ("truss_pair_setup", [C.POINTER(PairArgs), _vp]),
     ("truss_gcn_level_aggregate", [_vp, _i32, _vp]),
+    ("truss_optim_step", [C.POINTER(OptimArgs), _vp]),
 ]
 
 
@@ -175,6 +193,7 @@ class TrussLib:
         self.has_gcn_group = "truss_gcn_layer_group" in found                                # several split-weight layers in one launch
         self.has_pair_setup = "truss_pair_setup" in found                                    # the fused set-up of a chunk of pairs
         self.has_level_aggregate = "truss_gcn_level_aggregate" in found                      # a level's neighbour sums through the node table
+        self.has_optim_step = "truss_optim_step" in found                                    # clip and Adam of the update as one call
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")
         self.backend = d.truss_backend().decode()
