@@ -107,6 +107,19 @@ int truss_topo_solver_info(const truss_topo_t *t, int32_t *perm, int32_t *half_b
  * (TRUSS_F_EMIT_OBS), 0 when it queues the observation kernel behind it.  Same results either way. */
 int truss_topo_fused_obs(const truss_topo_t *t);
 
+/* LDS layout of the step launches of this topology, for tests and tools.  emit = 0: the plain step and the persistent
+ * rollout; 1: the launch that also writes the observations (where truss_topo_fused_obs() is 0 it has none and the plain
+ * layout is reported).  info[TRUSS_LDS_INFO_LEN], in this order: bytes per workgroup, offset of env 0, bytes between envs,
+ * envs per workgroup; window width W and band row stride, in doubles; band rows of team A and of team B; offset of team B's
+ * rows and of the trash slot from the band's start, in doubles; then byte ranges [lo, hi) inside one env: the band, the
+ * element-value buffer; the number of ranges in `live` and of entries in `band_offsets`.
+ * live[2 * cap_live]: (lo, hi) of everything that holds a value still to be read while the element-value buffer is in use.
+ * band_offsets[cap_offsets]: every offset (doubles from the band's start) the assembly tables store to, trash slot left out.
+ * Host pointers; live and band_offsets may be NULL. */
+#define TRUSS_LDS_INFO_LEN 16
+int truss_topo_lds_info(const truss_topo_t *t, int32_t emit, int32_t *info, int32_t *live, int32_t cap_live,
+                        int32_t *band_offsets, int32_t cap_offsets);
+
 /* ---- the batched environment step ----------------------------------------------------------
  * One Game_research04._game_modify(set_node, set_element, nC_e, actions) per env
  * (truss2D_ENV.py:370-525): clamp -> _set_model -> geometry move -> supports/round -> section

@@ -173,6 +173,34 @@ struct StepArgsDev {
 
 #define TRUSS_NRED 6  // vol, dt, con1, con2, energy, (spare)
 
+// Band row stride in doubles (kernel: StepLane::KS, host: TbGeometry) of a step-kernel instantiation.  A band row holds W = WL * RPL
+// entries.  Dense rows of W = 8 doubles are 64 bytes apart: the own-row fetches of a wave (ds_read_b128, 16-lane groups that mix
+// four teams of consecutive rows) then find every team on the same four bank quads, a 4-way conflict.  W + 2 doubles (80 bytes =
+// 5 quads, odd) put 16 consecutive rows on 16 different quads.  Padded: the 16-lane window-8 kernels of 5 elements per lane (the
+// metric configuration), plain step and persistent rollout -- measured, and their topologies keep their workgroups per CU.  Dense:
+// their EMIT twin (256 bytes below its fourth workgroup per CU); the variants that would lose a workgroup per CU on some topology
+// (<16,8,1,3>, <32,8,1,3>, <8,8,1,5>, the 16-wide windows); and the 8- / 32- / 64-lane kernels of 10 and 20 elements per lane,
+// which would not, but whose lane groups mix teams differently: the staggers of tb_band_team_b and tb_lds_layout are derived for
+// 16 lanes per env and nothing was measured there.  profiles/r19/README.md has the table.
+// -DTRUSS_BAND_PAD=0: dense rows everywhere (the A/B twin);
+// =2: every instantiation but the EMIT ones (diagnostic: the LDS table of the excluded variants).
+#ifndef TRUSS_BAND_PAD
+#define TRUSS_BAND_PAD 1
+#endif
+constexpr bool tb_band_padded(int G, int WL, int RPL, int EPL, bool emit) {
+  return TRUSS_BAND_PAD == 2 ? !emit : TRUSS_BAND_PAD != 0 && !emit && G == 16 && WL == 8 && RPL == 1 && EPL == 5;
+}
+constexpr int tb_band_stride(int G, int WL, int RPL, int EPL, bool emit) {
+  return WL * RPL + (tb_band_padded(G, WL, RPL, EPL, emit) ? 2 : 0);
+}
+// Where team B's band rows begin, in doubles from the band's start (kernel: StepLane::team_b, host: TbGeometry).  Dense rows: right
+// behind team A's rowsA rows.  Padded rows: the next offset that is 64 bytes (mod 128) behind team A -- the two teams of an env post
+// their halves of a pivot column with one ds_write_b64 (16-lane groups = one env, banks mod 32), and 8 + 8 consecutive doubles
+// that begin 64 bytes (mod 128) apart cover the 32 banks once.  (Rows are multiples of 16 bytes: so is the stagger.)
+constexpr int tb_band_team_b(int rowsA, int ks, int w) {
+  return rowsA * ks + (ks != w ? ((64 - rowsA * ks * 8) & 127) / 8 : 0);
+}
+
 TRUSS_HD float tb_clamp01(float v) { return v > 1.0f ? 1.0f : (v < 0.0f ? 0.0f : v); }
 
 // Python round(np.float32, 2): rint(v*100)/100 in float32 (truss2D_ENV.py:413)
@@ -187,6 +215,8 @@ TRUSS_HD float tb_round2(float v) { return rintf(v * 100.0f) / 100.0f; }
 template <int G, int WL, int RPL, int EPL, bool EMIT = false>
 struct StepLane {
   static constexpr int W = WL * RPL;
+  static constexpr int KS = tb_band_stride(G, WL, RPL, EPL, EMIT);   // doubles between band rows (the merge scratch keeps W)
+  static_assert(KS % 2 == 0, "band rows are read as 16-byte units");
   static constexpr int WL_ = WL;
   static constexpr int G_ = G;
   static constexpr bool EMIT_ = EMIT;
@@ -216,6 +246,7 @@ struct StepLane {
   float p_c1, p_c2;
 
   TRUSS_HD double *kb(const TopoDev &T) { return (double *)(L + T.o_kb); }
+  TRUSS_HD static int team_b(const TopoDev &T) { return tb_band_team_b(T.rowsA, KS, W); }
   TRUSS_HD double *zs(const TopoDev &T) { return (double *)(L + T.o_zs); }
   TRUSS_HD double *xsol(const TopoDev &T) { return (double *)(L + T.o_xsol); }
   TRUSS_HD double *red(const TopoDev &T) { return (double *)(L + T.o_red); }
@@ -264,7 +295,7 @@ struct StepLane {
     envc = active ? env : A.B - 1;
     TB = lds;
     L = lds + T.o_env0 + (size_t)grp * T.env_stride;
-    Kt = (double *)(L + T.o_kb) + team * T.rowsA * W;
+    Kt = (double *)(L + T.o_kb) + team * team_b(T);
     Zt = (double *)(L + T.o_zs) + team * T.zlen;     // zlen is even: 16-byte aligned teams
     ZRt = (double *)(L + T.o_zring) + team * W;    // adjacent banks for the two teams
     bad = 0;
@@ -337,11 +368,13 @@ struct StepLane {
   }
 
   // clear the band with 16-byte stores (padding-row identity is written after the next barrier).  The
-  // band geometry comes with the kernel arguments, not with the blob being staged.
+  // band geometry comes with the kernel arguments, not with the blob being staged.  Padded rows: the padding is cleared with the
+  // rows, a quarter more stores (24 instead of 19 per lane at 32 nodes).  Skipping it with index arithmetic in the loop
+  // (row = i / (W / 2), ...) cost 600 cycles more than the stores it saved (profiles/r19/README.md).
   TRUSS_HD void band_clear(const TopoDev &T) {
     tb_u4 *K4 = (tb_u4 *)kb(T);
     const tb_u4 z = {0u, 0u, 0u, 0u};
-    const int tot4 = ((T.rowsA + T.rowsB) * W) >> 1;
+    const int tot4 = (KS == W ? (T.rowsA + T.rowsB) * W : team_b(T) + T.rowsB * KS) >> 1;
     for (int i = g; i < tot4; i += G) K4[i] = z;
   }
 
@@ -832,8 +865,8 @@ struct StepLane {
     // identity rows: team A beyond its part + middle; team B beyond the middle (its middle rows keep a
     // zero diagonal: they are never pivots of team B)
     const int idA = T.nteams == 1 ? T.ndof : T.ndof - T.KA;
-    for (int r = idA + g; r < T.rowsA; r += G) K[r * W + r % W] = 1.0;
-    for (int r = T.KA + T.mid + g; r < T.rowsB; r += G) K[(T.rowsA + r) * W + r % W] = 1.0;
+    for (int r = idA + g; r < T.rowsA; r += G) K[r * KS + r % W] = 1.0;
+    for (int r = T.KA + T.mid + g; r < T.rowsB; r += G) K[team_b(T) + r * KS + r % W] = 1.0;
   }
 
   // ---- phase 5b: the element-value buffer is dead; its bytes become the solver scratch ----
@@ -882,7 +915,7 @@ struct StepLane {
     for (int s = 0; s < RPL; ++s) {
       int r = gs + WL * s;
 #pragma unroll
-      for (int c = 0; c < W; ++c) R[s][c] = (c <= r) ? Kt[r * W + c] : Kt[c * W + r];  // band rows are stored by column residue
+      for (int c = 0; c < W; ++c) R[s][c] = (c <= r) ? Kt[r * KS + c] : Kt[c * KS + r];  // band rows are stored by column residue
       rhs[s] = Zt[r];
     }
 #pragma unroll
@@ -897,7 +930,7 @@ struct StepLane {
   double zkeep[RPL];
   TRUSS_HD void pivot_write(const TopoDev &T, int k, int kk) {
 #pragma unroll
-    for (int s = 0; s < RPL; ++s) Kt[k * W + gs + WL * s] = R[s][kk];
+    for (int s = 0; s < RPL; ++s) Kt[k * KS + gs + WL * s] = R[s][kk];
     bx = rhs[kk / WL];
   }
   // rows kb + (gs + WL s - c) mod W for a block that starts at window slot c (c = 0 for the clean blocks)
@@ -913,13 +946,13 @@ struct StepLane {
   TRUSS_HD void pivot_update(const TopoDev &T, int k, int kk) {
     double col[W];
     {  // this lane's entries of the entering column k+W: static data, requested before the posted column
-      const double *Kn = Kt + (k + W) * W;
+      const double *Kn = Kt + (k + W) * KS;
 #pragma unroll
       for (int s = 0; s < RPL; ++s) ecol[s] = Kn[gs + WL * s];
     }
 #pragma unroll
     for (int i = 0; i < W / 2; ++i) {
-      tb_d2 v = ((const tb_d2 *)__builtin_assume_aligned(Kt + k * W, 16))[i];
+      tb_d2 v = ((const tb_d2 *)__builtin_assume_aligned(Kt + k * KS, 16))[i];
       col[2 * i] = v[0];
       col[2 * i + 1] = v[1];
     }
@@ -937,7 +970,7 @@ struct StepLane {
     }
     // the window slides: column k leaves, column k+W enters; the pivot row's lane adopts row k+W, which
     // it requested at the start of this block of W pivots (factor_rows_fetch).  Band rows are stored by
-    // column residue (entry (r, c) at r*W + c%W): a row maps straight onto the window registers and every
+    // column residue (entry (r, c) at r*KS + c%W): a row maps straight onto the window registers and every
     // other lane finds its entry of the new column at its own residue.
 #pragma unroll
     for (int s = 0; s < RPL; ++s) R[s][kk] = ecol[s];
@@ -958,7 +991,7 @@ struct StepLane {
 #pragma unroll
     for (int s = 0; s < RPL; ++s) {
       const int rn = kb + W + gs + WL * s;
-      const tb_d2 *K2 = (const tb_d2 *)__builtin_assume_aligned(Kt + rn * W, 16);
+      const tb_d2 *K2 = (const tb_d2 *)__builtin_assume_aligned(Kt + rn * KS, 16);
 #pragma unroll
       for (int i = 0; i < W / 2; ++i) {
         tb_d2 v = K2[i];
@@ -975,7 +1008,7 @@ struct StepLane {
   TRUSS_HD void pivot_check(const TopoDev &T) {
     const int lim = (T.nteams == 2 && team == 1) ? T.KA : (T.nteams == 2 ? T.KA + W : T.KA);
     for (int k = gs; k < lim; k += WL) {
-      const double d = Kt[k * W + k % W];
+      const double d = Kt[k * KS + k % W];
       if (!(d > 0.0) || !(d < 1.7e308)) bad = 1;
     }
   }
@@ -1045,7 +1078,7 @@ struct StepLane {
     for (int s = 0; s < RPL; ++s) {
       const int p = kb + gs + WL * s;
       const int pc = p < 0 ? 0 : p;
-      const tb_d2 *K2 = (const tb_d2 *)__builtin_assume_aligned(Kt + pc * W, 16);
+      const tb_d2 *K2 = (const tb_d2 *)__builtin_assume_aligned(Kt + pc * KS, 16);
 #pragma unroll
       for (int i = 0; i < W / 2; ++i) {
         tb_d2 v = K2[i];
@@ -1053,7 +1086,7 @@ struct StepLane {
         nc[s][2 * i + 1] = v[1];
       }
       nz[s] = Zt[pc];
-      nd[s] = Kt[pc * W + pc % W];   // the pivot d_p (a register array must not be indexed by the lane id)
+      nd[s] = Kt[pc * KS + pc % W];   // the pivot d_p (a register array must not be indexed by the lane id)
     }
   }
   // 1/d_p of the fetched rows: the same operations as in the factorisation, so the same bits; once per block and lane,

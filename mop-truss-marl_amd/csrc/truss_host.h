@@ -119,6 +119,15 @@ static int32_t tb_push(std::vector<char> &blob, const std::vector<T> &v) {
   return (int32_t)off;
 }
 
+struct TbFrag {   // a byte range [lo, hi) inside one env's LDS region
+  size_t lo, hi;
+};
+// what truss_topo_lds_info reports of one layout: byte ranges inside an env
+struct TbLayoutInfo {
+  TbFrag band{}, ev{};
+  std::vector<TbFrag> live_with_ev;   // what holds a value somebody still reads while the element values are in their buffer
+};
+
 struct truss_topo {
   int N = 0, E = 0, NP = 0, ndof = 0, n_pad = 0, n_rest = 0, bw = 0;
   int G = 0, WL = 0, RPL = 0, EPL = 0, W = 0, variant = -1;
@@ -130,6 +139,9 @@ struct truss_topo {
   void *etab = nullptr;   // ... and the emission tables of the fused observation writer (TopoDev::etab)
   size_t lds_bytes = 0;
   int n_sections = 0;
+  // for truss_topo_lds_info, [0] plain / rollout launches, [1] EMIT launches: the band offsets the tables hold, the layout's ranges
+  std::vector<int32_t> band_offsets[2];
+  TbLayoutInfo layout[2];
   truss_topo() = default;
   truss_topo(const truss_topo &) = delete;
   truss_topo &operator=(const truss_topo &) = delete;
@@ -148,12 +160,8 @@ struct truss_topo {
 // Builds the register tables (t->etab, uploaded here) and appends the LDS-resident nN_x_e table to `blob`.
 // Returns false when the topology is outside what the fused writer covers; truss_step then runs the observation
 // kernel as a second launch.
-struct TbFrag {
-  size_t lo, hi;
-};
-static bool tb_build_emit(truss_topo *t, const int32_t *conn, const uint8_t *res, const uint8_t *top,
+static bool tb_build_emit(truss_topo *t, TopoDev &D, const int32_t *conn, const uint8_t *res, const uint8_t *top,
                           std::vector<TbFrag> early, std::vector<TbFrag> late, std::vector<char> &blob) {
-  TopoDev &D = t->dev;
   const int N = t->N, E = t->E, G = t->G;
   D.emit_ok = 0;
   if (!tb_variant_emits(t->G, t->WL, t->RPL, t->EPL) || tb_env_int("TRUSS_NO_FUSED_OBS", 0)) return false;
@@ -426,9 +434,10 @@ static bool tb_node_ordering(const TbInput &in, int &bw, std::vector<int> &dofpo
 }
 
 // ---- kernel variant (index into kVariants, -1 = none compiled): the narrowest window that holds the band; 16 lanes per
-// env (4 envs per wave) so that a 4096-env batch puts a wave on every SIMD.  TRUSS_LANES / TRUSS_WLANES / TRUSS_RPL override ----
+// env (4 envs per wave) so that a 4096-env batch puts a wave on every SIMD.  TRUSS_LANES / TRUSS_WLANES / TRUSS_RPL / TRUSS_EPL override ----
 static int tb_pick_variant(int bw, int E) {
-  int want_G = tb_env_int("TRUSS_LANES", 0), want_WL = tb_env_int("TRUSS_WLANES", 0), want_RPL = tb_env_int("TRUSS_RPL", 0);
+  int want_G = tb_env_int("TRUSS_LANES", 0), want_WL = tb_env_int("TRUSS_WLANES", 0), want_RPL = tb_env_int("TRUSS_RPL", 0),
+      want_EPL = tb_env_int("TRUSS_EPL", 0);
   int pick = -1;
   auto score = [](const TbVariant &v) {
     int W = v.WL * v.RPL;
@@ -443,15 +452,19 @@ static int tb_pick_variant(int bw, int E) {
     if (want_G && v.G != want_G) continue;
     if (want_WL && v.WL != want_WL) continue;
     if (want_RPL && v.RPL != want_RPL) continue;
+    if (want_EPL && v.EPL != want_EPL) continue;
     if (pick < 0 || score(v) < score(kVariants[pick])) pick = i;
   }
   return pick;
 }
 
 // ---- solver geometry (see TopoDev): one team, or two that eliminate from both ends (TRUSS_ONE_SIDED: diagnostic) ----
+// The band of one layout: rows KS doubles apart (tb_band_stride: W, or W + 2 where rows are padded), team A's rows first, team B's
+// from kb_b (tb_band_team_b, the function the kernel takes it from; tools/lds_conflict_model.cpp sets other values to compare them).
 struct TbGeometry {
-  int nteams, W, n, KA, mid, rowsA, rowsB, zlen, dlen, zslot;
-  explicit TbGeometry(const truss_topo &t) : W(t.W), n(t.ndof) {
+  int nteams, W, KS, n, KA, mid, rowsA, rowsB, zlen, dlen, zslot, kb_b;
+  bool padded() const { return KS != W; }
+  TbGeometry(const truss_topo &t, int ks) : W(t.W), KS(ks), n(t.ndof) {
     nteams = (t.G / t.WL >= 2 && t.RPL == 1 && !tb_env_int("TRUSS_ONE_SIDED", 0)) ? 2 : 1;
     if (nteams == 2) {
       KA = n > W ? (n - W + 1) / 2 : 0;
@@ -468,17 +481,18 @@ struct TbGeometry {
       zlen = dlen = t.n_pad + W;
       zslot = t.n_pad;
     }
+    kb_b = tb_band_team_b(rowsA, KS, W);   // one team (rowsB = 0): where the trash slot lies
   }
   // offset (in doubles) of the lower-band entry (r, c), r >= c, original solver positions.  A band row
-  // stores its W entries by COLUMN RESIDUE in the owning team's frame: entry (row, col) at row*W + col%W
+  // stores its W entries by COLUMN RESIDUE in the owning team's frame: entry (row, col) at row*KS + col%W
   // (distinct for the W consecutive columns of a row), which is the order of the solver's window registers.
   int band_off(int r, int c) const {
-    if (nteams == 1 || r < n - KA) return r * W + (c % W);              // team A: its part + middle rows
+    if (nteams == 1 || r < n - KA) return r * KS + (c % W);             // team A: its part + middle rows
     int rb = n - 1 - r, cb = n - 1 - c;                                    // team B frame: cb >= rb
-    return (rowsA + cb) * W + (rb % W);
+    return kb_b + cb * KS + (rb % W);
   }
   // a spare double right behind the band: sink for entries on restrained DOFs
-  int trash_off() const { return (rowsA + rowsB) * W; }
+  int trash_off() const { return kb_b + rowsB * KS; }
 };
 
 // ---- topology tables ----
@@ -597,10 +611,10 @@ static std::vector<int16_t> tb_solution_slots(const TbGeometry &g, const TbInput
 
 static std::vector<int16_t> tb_int16(const int32_t *p, size_t n) { return std::vector<int16_t>(p, p + n); }
 
-// every table of the step kernel, packed into `blob`; the ORDER of the pushes is the blob layout.  Fills the counts, the
-// solver geometry and the f_* offsets of t.dev.  Refuses (band guard, then node degree) before anything is pushed.
-static int tb_build_tables(truss_topo &t, const TbGeometry &g, const TbInput &in, const std::vector<int> &dofpos,
-                           const std::vector<int16_t> &pairs, std::vector<char> &blob) {
+// every table of the step kernel for the band of `g`, packed into `blob`; the ORDER of the pushes is the blob layout.  Fills the
+// counts, the solver geometry and the f_* offsets of D (the plain launches' or the EMIT launches' TopoDev).  Refuses (band guard, then node degree) before anything is pushed.
+static int tb_build_tables(truss_topo &t, TopoDev &D, const TbGeometry &g, const TbInput &in, const std::vector<int> &dofpos,
+                           const std::vector<int16_t> &pairs, std::vector<char> &blob, std::vector<int32_t> &band_offsets) {
   const int S = in.n_sections;
   std::vector<int16_t> posnode, dofpos16, restslot, asm_code, adj8;
   tb_position_tables(t, dofpos, posnode, dofpos16, restslot);
@@ -616,7 +630,12 @@ static int tb_build_tables(truss_topo &t, const TbGeometry &g, const TbInput &in
     areaf[i] = (float)area[i];
     vsf[i] = (float)(area[i] / in.sections[2 * (S - 1)]);   // truss2D_ENV.py:86-87 (area / truss[-1] area)
   }
-  TopoDev &D = t.dev;
+  const std::vector<int16_t> diagoff = tb_diag_offsets(g, t.N, dofpos);
+  band_offsets.clear();     // what the two tables say about the band (truss_topo_lds_info): every entry that is not the trash slot
+  for (int16_t c : asm_code)
+    if (c != g.trash_off()) band_offsets.push_back(c);
+  for (int16_t c : diagoff)
+    if (c != g.trash_off()) band_offsets.push_back(c);
   D.N = t.N;
   D.E = t.E;
   D.NP = t.NP;
@@ -651,7 +670,7 @@ static int tb_build_tables(truss_topo &t, const TbGeometry &g, const TbInput &in
   D.f_areaf = tb_push(blob, areaf);
   D.f_vsf = tb_push(blob, vsf);
   D.f_adj8 = tb_push(blob, adj8);
-  D.f_diagoff = tb_push(blob, tb_diag_offsets(g, t.N, dofpos));
+  D.f_diagoff = tb_push(blob, diagoff);
   D.f_zcode = tb_push(blob, tb_load_codes(g, posnode, nflags));
   D.f_exs = tb_push(blob, tb_solution_slots(g, in, dofpos));
   blob.resize((blob.size() + 15) & ~size_t(15));
@@ -660,7 +679,7 @@ static int tb_build_tables(truss_topo &t, const TbGeometry &g, const TbInput &in
 }
 
 // ---- LDS layout: [copy of the tables][env 0][env 1]...; every array 16-byte aligned.  Fills o_*, so_*, env_stride and o_env0
-// of t.dev and t.lds_bytes; early / late: the dead bytes of an env for the bank of the fused observation writer (tb_build_emit) ----
+// of D for the band of `g` and returns the bytes per workgroup; early / late: the dead bytes of an env for the bank of the fused observation writer (tb_build_emit) ----
 struct TbCarve {   // byte offsets of arrays laid out one behind the other
   size_t off = 0;
   int32_t operator()(size_t bytes) {
@@ -672,13 +691,21 @@ struct TbCarve {   // byte offsets of arrays laid out one behind the other
     if (off - o0 < need) off = (o0 + need + 15) & ~size_t(15);
   }
 };
-static void tb_lds_layout(truss_topo &t, const TbGeometry &g, size_t table_bytes, std::vector<TbFrag> &early, std::vector<TbFrag> &late) {
-  TopoDev &D = t.dev;
+// Two orders.  Dense bands (every EMIT layout among them, whose early / late fragments are placed from it):
+//   [band][solver scratch | EV][par][y][x][tg][geo tac | merge scratch][sec]
+// the element values (EV, 3 (E + 1) doubles, live from phase_elements to phase_assemble_nodes) lie over the solver scratch, which is
+// smaller, so the region is as long as EV.  Padded bands have no bytes to spare for that:
+//   [band][solver scratch][geo tac | merge scratch][par][y][x][tg][sec]
+// the action rows are dead from the end of phase_sizing until rollout_stash / merge_post, both behind the assembly, so EV runs on
+// from the solver scratch into them and nothing is carved for EV alone.
+static size_t tb_lds_layout(const truss_topo &t, TopoDev &D, const TbGeometry &g, size_t table_bytes, std::vector<TbFrag> &early,
+                            std::vector<TbFrag> &late, TbLayoutInfo &info) {
   const int N = t.N, E = t.E, W = g.W;
+  const size_t ev_bytes = sizeof(double) * 3 * ((size_t)E + 1);
   TbCarve carve;
   // band region; after the back substitution it is reused as the output staging area
   {
-    const size_t band = sizeof(double) * ((size_t)(g.rowsA + g.rowsB) * W + 2);  // + trash slot
+    const size_t band = sizeof(double) * ((size_t)g.trash_off() + 2);  // + trash slot
     TbCarve sub;
     D.so_q0 = sub(sizeof(float) * E);
     D.so_sr = sub(sizeof(float) * E);
@@ -691,38 +718,58 @@ static void tb_lds_layout(truss_topo &t, const TbGeometry &g, size_t table_bytes
     D.o_kb = carve(std::max(band, so));
     D.o_red = D.o_kb + (int32_t)red_off;
     early.push_back({(size_t)D.o_kb + so, (size_t)D.o_kb + std::max(band, so)});
+    info.band = {(size_t)D.o_kb, (size_t)D.o_kb + band};
   }
   // solver scratch; before the solver the same bytes hold the per-element (k cc, k cs, k ss), after
   // the back substitution `red` (objective partials) reuses the z vectors
-  {
-    const size_t o0 = carve.off;
-    D.o_zs = carve(sizeof(double) * (size_t)g.zlen * g.nteams);  // z vector per team (zlen is even)
-    D.o_xsol = carve(sizeof(double) * (g.zslot + 4));  // + zero slot, dummy slot, 16-byte fill
-    D.o_rbuf = carve(sizeof(double) * std::max(t.n_rest, 1));
-    D.o_zring = carve(sizeof(double) * W * g.nteams);   // per-lane trash slots
-    D.o_ev = (int32_t)o0;
-    carve.at_least(o0, sizeof(double) * 3 * ((size_t)E + 1));
-    late.push_back({o0, (size_t)D.o_rbuf});                     // z vectors, solution vector
-    late.push_back({(size_t)D.o_zring, carve.off});              // behind the reactions
-  }
-  D.o_par = carve(sizeof(double) * 8);
-  D.o_y = carve(sizeof(float) * N);
-  D.o_x = carve(sizeof(float) * N);
-  D.o_tg = carve(sizeof(float) * N);
-  {
+  const size_t scratch0 = carve.off;
+  D.o_zs = carve(sizeof(double) * (size_t)g.zlen * g.nteams);  // z vector per team (zlen is even)
+  D.o_xsol = carve(sizeof(double) * (g.zslot + 4));  // + zero slot, dummy slot, 16-byte fill
+  D.o_rbuf = carve(sizeof(double) * std::max(t.n_rest, 1));
+  D.o_zring = carve(sizeof(double) * W * g.nteams);   // per-lane trash slots
+  D.o_ev = (int32_t)scratch0;
+  info.ev = {scratch0, scratch0 + ev_bytes};
+  auto actions = [&]() {
     const size_t o0 = carve.off;
     D.o_geo = carve(sizeof(float) * 2 * N);
     D.o_tac = carve(sizeof(float) * 3 * N);
     D.o_mrg = (int32_t)o0;  // merge scratch of the two-sided solver: the actions are dead by then
     carve.at_least(o0, g.nteams == 2 ? sizeof(double) * (size_t)(W * W + W) : 0);
     early.push_back({o0, carve.off});
+  };
+  auto rows = [&]() {
+    D.o_par = carve(sizeof(double) * 8);
+    D.o_y = carve(sizeof(float) * N);
+    D.o_x = carve(sizeof(float) * N);
+    D.o_tg = carve(sizeof(float) * N);
+    info.live_with_ev.push_back({(size_t)D.o_par, carve.off});
+  };
+  if (g.padded()) {
+    actions();
+    carve.at_least(scratch0, ev_bytes);
+    late.push_back({scratch0, (size_t)D.o_rbuf});
+    late.push_back({(size_t)D.o_zring, (size_t)D.o_geo});
+    rows();
+  } else {
+    carve.at_least(scratch0, ev_bytes);
+    late.push_back({scratch0, (size_t)D.o_rbuf});                // z vectors, solution vector
+    late.push_back({(size_t)D.o_zring, carve.off});              // behind the reactions
+    rows();
+    actions();
   }
   D.o_sec = carve(sizeof(int32_t) * E);
-  // stagger env regions across LDS banks: stride = 64 B (mod 256 B)
-  const size_t stride = ((carve.off + 255) & ~size_t(255)) + 64;
+  info.live_with_ev.push_back({(size_t)D.o_sec, carve.off});
+  // Env regions are staggered across the LDS banks.  Dense bands: stride = 64 B (mod 256 B).  Padded bands: 128 B (mod 256 B) --
+  // a 16-lane group of the pivot column's broadcast read (ds_read_b128, banks mod 64) holds the two teams of two neighbouring envs,
+  // four addresses that must lie on four different 16-byte bank quads: team B is 64 B (mod 128 B) behind team A (TbGeometry), the
+  // next env 128 B (mod 256 B) behind this one.  The 32-lane groups of the entering column's read (ds_read_b64: four runs of 64 B)
+  // then tile the 256 bytes of the banks as well.  tools/lds_conflict_model.cpp counts every row-structured access for both.
+  const size_t stagger = g.padded() ? 128 : 64;
+  const size_t stride = ((carve.off + 255) & ~size_t(255)) + stagger;
+  info.live_with_ev.push_back({stride - 4, stride});   // the parked symmetry coin (StepLane::coinsh)
   D.env_stride = (int32_t)stride;
   D.o_env0 = (int32_t)((table_bytes + 255) & ~size_t(255));
-  t.lds_bytes = D.o_env0 + stride * (64 / t.G);
+  return D.o_env0 + stride * (64 / t.G);
 }
 
 extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const int32_t *conn, const uint8_t *res,
@@ -758,29 +805,46 @@ extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const
   t->EPL = v.EPL;
   t->W = v.WL * v.RPL;
   t->n_pad = ((t->ndof + t->W - 1) / t->W) * t->W;
-  const TbGeometry g(*t);
-  std::vector<char> blob;
-  if (int rc = tb_build_tables(*t, g, in, dofpos, pairs, blob)) return rc;
+  // Two sets of tables and two layouts: the plain step and the persistent rollout with the band rows of their instantiation
+  // (tb_band_stride), the EMIT instantiation with dense rows.  One device allocation holds [plain tables][EMIT tables].
+  const TbGeometry g(*t, tb_band_stride(t->G, t->WL, t->RPL, t->EPL, false)), ge(*t, tb_band_stride(t->G, t->WL, t->RPL, t->EPL, true));
+  TopoDev &D = t->dev, &DE = t->dev_emit;
+  std::vector<char> blob, blob_e;
+  if (int rc = tb_build_tables(*t, D, g, in, dofpos, pairs, blob, t->band_offsets[0])) return rc;
   std::vector<TbFrag> fr_early, fr_late;
-  tb_lds_layout(*t, g, blob.size(), fr_early, fr_late);
-  tb_build_emit(t.get(), conn, res, top, fr_early, fr_late, blob);   // may append the LDS-resident nN_x_e table to the blob
-  t->blob = tb_dev_alloc(blob.size());
-  if (!t->blob || !tb_dev_upload(t->blob, blob.data(), blob.size()))
+  t->lds_bytes = tb_lds_layout(*t, D, g, blob.size(), fr_early, fr_late, t->layout[0]);
+  if (tb_variant_emits(t->G, t->WL, t->RPL, t->EPL)) {
+    if (int rc = tb_build_tables(*t, DE, ge, in, dofpos, pairs, blob_e, t->band_offsets[1])) return rc;
+    fr_early.clear();
+    fr_late.clear();
+    tb_lds_layout(*t, DE, ge, blob_e.size(), fr_early, fr_late, t->layout[1]);
+    tb_build_emit(t.get(), DE, conn, res, top, fr_early, fr_late, blob_e);   // may append the LDS-resident nN_x_e table to the blob
+  }
+  const size_t emit_at = (blob.size() + 255) & ~size_t(255);
+  t->blob = tb_dev_alloc(emit_at + blob_e.size());
+  if (!t->blob || !tb_dev_upload(t->blob, blob.data(), blob.size()) ||
+      (!blob_e.empty() && !tb_dev_upload((char *)t->blob + emit_at, blob_e.data(), blob_e.size())))
     return tb_fail(TRUSS_ENOMEM, "device allocation/upload of topology tables failed");
-  TopoDev &D = t->dev;
   const size_t stride = (size_t)D.env_stride;
   D.blob = (const char *)t->blob;
-  t->dev_emit = D;
-  t->dev_emit.blob_bytes = (int32_t)blob.size();
-  t->dev_emit.o_flag = (int32_t)blob.size();   // progress word right behind the staged tables
-  t->dev_emit.o_env0 = (int32_t)((blob.size() + 16 + 255) & ~size_t(255));
-  t->lds_bytes_emit = t->dev_emit.o_env0 + stride * (64 / t->G);
-  if (D.emit_ok && t->lds_bytes_emit > 160 * 1024) D.emit_ok = t->dev_emit.emit_ok = 0;
+  if (DE.emit_ok) {
+    DE.blob = (const char *)t->blob + emit_at;
+    DE.blob_bytes = (int32_t)blob_e.size();
+    DE.o_flag = (int32_t)blob_e.size();   // progress word right behind the staged tables
+    DE.o_env0 = (int32_t)((blob_e.size() + 16 + 255) & ~size_t(255));
+    t->lds_bytes_emit = DE.o_env0 + (size_t)DE.env_stride * (64 / t->G);
+    if (t->lds_bytes_emit > 160 * 1024) DE.emit_ok = 0;
+  }
+  if (!DE.emit_ok) {     // no EMIT launch will be asked for (tb_step_dispatch goes by dev.emit_ok)
+    DE = D;
+    t->lds_bytes_emit = t->lds_bytes;
+  }
+  D.emit_ok = DE.emit_ok;
   if (tb_env_int("TRUSS_VERBOSE", 0))
     fprintf(stderr,
-            "[truss_mi355] N=%d E=%d ndof=%d bw=%d | G=%d WL=%d RPL=%d EPL=%d teams=%d KA=%d mid=%d | tables %d B, "
+            "[truss_mi355] N=%d E=%d ndof=%d bw=%d | G=%d WL=%d RPL=%d EPL=%d teams=%d KA=%d mid=%d | band rows %d B apart, tables %d B, "
             "env %zu B, LDS/workgroup %zu B (%zu workgroups/CU), fused observation writer %s\n",
-            N, E, t->ndof, t->bw, t->G, t->WL, t->RPL, t->EPL, g.nteams, g.KA, g.mid, D.blob_bytes, stride, t->lds_bytes,
+            N, E, t->ndof, t->bw, t->G, t->WL, t->RPL, t->EPL, g.nteams, g.KA, g.mid, 8 * g.KS, D.blob_bytes, stride, t->lds_bytes,
             (size_t)(160 * 1024) / t->lds_bytes, D.emit_ok ? "yes" : "no");
   if (tb_env_int("TRUSS_VERBOSE", 0) && D.emit_ok)
     fprintf(stderr, "[truss_mi355]   fused launch: tables %d B, LDS/workgroup %zu B (%zu workgroups/CU)\n", t->dev_emit.blob_bytes,
@@ -813,6 +877,26 @@ extern "C" int truss_topo_solver_info(const truss_topo_t *t, int32_t *perm, int3
 }
 
 extern "C" int truss_topo_fused_obs(const truss_topo_t *t) { return t && t->dev.emit_ok ? 1 : 0; }
+
+extern "C" int truss_topo_lds_info(const truss_topo_t *t, int32_t emit, int32_t *info, int32_t *live, int32_t cap_live,
+                                   int32_t *band_offsets, int32_t cap_offsets) {
+  if (!t || !info) return tb_fail(TRUSS_EINVAL, "NULL argument");
+  const int which = emit && t->dev.emit_ok ? 1 : 0;
+  const TopoDev &D = which ? t->dev_emit : t->dev;
+  const TbLayoutInfo &I = t->layout[which];
+  const TbGeometry g(*t, tb_band_stride(t->G, t->WL, t->RPL, t->EPL, which != 0));
+  const int32_t v[TRUSS_LDS_INFO_LEN] = {(int32_t)(which ? t->lds_bytes_emit : t->lds_bytes), D.o_env0, D.env_stride, 64 / t->G, g.W, g.KS,
+                                         g.rowsA, g.rowsB, g.kb_b, g.trash_off(), (int32_t)I.band.lo, (int32_t)I.band.hi,
+                                         (int32_t)I.ev.lo, (int32_t)I.ev.hi, (int32_t)I.live_with_ev.size(),
+                                         (int32_t)t->band_offsets[which].size()};
+  memcpy(info, v, sizeof v);
+  for (int i = 0; live && i < cap_live && i < (int)I.live_with_ev.size(); ++i) {
+    live[2 * i] = (int32_t)I.live_with_ev[i].lo;
+    live[2 * i + 1] = (int32_t)I.live_with_ev[i].hi;
+  }
+  for (int i = 0; band_offsets && i < cap_offsets && i < (int)t->band_offsets[which].size(); ++i) band_offsets[i] = t->band_offsets[which][i];
+  return TRUSS_OK;
+}
 
 static int tb_make_step_args(const truss_topo_t *t, const truss_step_args_t *a, StepArgsDev &D) {
   if (!t || !a) return tb_fail(TRUSS_EINVAL, "NULL argument");

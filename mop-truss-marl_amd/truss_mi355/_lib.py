@@ -155,6 +155,7 @@ _LATER_ENTRIES = [
     ("truss_pair_setup", [C.POINTER(PairArgs), _vp]),
     ("truss_gcn_level_aggregate", [_vp, _i32, _vp]),
     ("truss_optim_step", [C.POINTER(OptimArgs), _vp]),
+    ("truss_topo_lds_info", [_vp, _i32, _vp, _vp, _i32, _vp, _i32]),
 ]
 
 
