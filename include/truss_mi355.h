@@ -752,6 +752,70 @@ typedef struct truss_optim_args {
 } truss_optim_args_t;
 int truss_optim_step(const truss_optim_args_t *args, void *stream);
 
+/* ---- critic tail: the 11 sum pools, their concatenation and the three dense layers of a critic pass, forward and backward ----
+ * replaces: the end of truss2D_RL._critic_steps behind the second GCN level (torch.stack(o, 1).sum(2).flatten(1), dense_1 / relu,
+ * dense_2 / relu, dense_out) and its autograd backward.  One ITEM is one critic pass; a call takes any number of independent items
+ * that may differ in every size.  Item sizes: B samples, N nodes, L layers of H channels, Q dense units; K1 = L H.  All float32,
+ * u = 2^-24 roundings as written, nothing contracted.  Forward, for sample b:
+ *   p[b][i H + c] = ((O_i[b][0][c] + O_i[b][1][c]) + O_i[b][2][c]) + ...           over the N nodes in ascending order
+ *   a1 = W1 p + b1 (W1 [Q][K1]), z1 = max(a1, 0);  a2 = W2 z1 + b2 (W2 [Q][Q]), z2 = max(a2, 0);  q = w3 . z2 + b3
+ *   every dot product of a row w with x over K terms: lane l of 64 owns the element quads l, l + 64, ... and adds w_k x_k to its own
+ *   partial sum (from 0) in ascending k; the 64 partials are added pairwise -- lanes 2m and 2m + 1, then pairs of those, six levels;
+ *   the bias is added last.
+ * A workgroup owns TRUSS_CRITIC_TAIL_SAMPLES consecutive samples of one item end to end; one launch per TRUSS_CRITIC_TAIL_MAX items
+ * (longer lists run as consecutive launches).  16-byte loads where the row length (H, K1, Q) is a multiple of 4 and the pointers
+ * are 16-byte aligned, word by word otherwise: the same sums either way.
+ *   o[i]   device [B][N][H] contiguous, i < n_layers           w1 [Q][K1], b1 [Q], w2 [Q][Q], b2 [Q], w3 [Q], b3 [1]  device
+ *   q      device [B], written
+ *   save   != 0: p [B][K1], z1 [B][Q], z2 [B][Q] are written too (what the backward reads); == 0: they are not touched (may be NULL)
+ * Backward of an item, from dq (sample b at dq[b dq_stride]) and the saved p, z1, z2 -- launch A, per sample:
+ *   dz2_k = (dq w3_k) [z2_k > 0]                                                    one rounding
+ *   dz1_j = (sum_k dz2_k W2[k][j]) [z1_j > 0],   dp_m = sum_j dz1_j W1[j][m]         from 0, ascending k / j, one owner per element
+ *   d_o[i][b][n][c] = dp[b][i H + c] for every node n, for the layers whose d_o[i] is not NULL
+ * and, when any parameter gradient is asked for, dz1 / dz2 [B][Q] go to the caller's scratch and launch B adds over the samples in
+ * ascending b, from 0, one owner per element -- each of the six is optional (NULL: not wanted):
+ *   d_w1 = dz1^T p   d_b1 = sum_b dz1   d_w2 = dz2^T z1   d_b2 = sum_b dz2   d_w3 = sum_b dq z2   d_b3 = sum_b dq
+ * An item that asks for nothing (no d_o, no parameter gradient) is skipped.  p is read only for d_w1.
+ * o[i] (optional) names the level outputs [B][N][H] the forward pooled: the backward does not read them, but whoever produced them
+ * still does, so an output of the call that overlaps one of them is refused like an overlap with an input.
+ * The descriptors travel in the kernel arguments: the entries allocate nothing and do not synchronise; capturable.  Every output
+ * element has one owner and every sum a fixed order (no atomics): two calls on equal inputs give equal bits.
+ * With nothing launched or written -- TRUSS_EINVAL: NULL items with n_items > 0, n_items < 0, a bad struct_size, a size < 1
+ * (n_batch < 0, dq_stride < 0), a NULL required pointer (forward: o[i], the six parameters, q, and p / z1 / z2 with save; backward: dq, z1, z2, w1,
+ * w2, w3, p with d_w1, dz1 and dz2 with any parameter gradient), an output of the call overlapping an input or another output of
+ * the call (any item); TRUSS_EUNSUPPORTED: n_layers > TRUSS_CRITIC_TAIL_MAX_LAYERS, n_hidden > 256, n_q > 256, K1 > 4096,
+ * n_nodes > 2^23 - 1.
+ * n_items == 0: TRUSS_OK, no launch; an item with n_batch == 0 is skipped.  Optional entries of ABI version 3 (a library may
+ * lack them). */
+#define TRUSS_CRITIC_TAIL_MAX 4            /* items per launch */
+#define TRUSS_CRITIC_TAIL_MAX_LAYERS 16
+#ifndef TRUSS_CRITIC_TAIL_SAMPLES
+#define TRUSS_CRITIC_TAIL_SAMPLES 1        /* samples per workgroup (a build-time choice: 1 .. 8) */
+#endif
+typedef struct truss_critic_tail_args {
+  size_t struct_size;
+  int32_t n_batch, n_nodes, n_layers, n_hidden, n_q;
+  int32_t save;
+  const float *o[TRUSS_CRITIC_TAIL_MAX_LAYERS];
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+  float *q;
+  float *p, *z1, *z2;
+} truss_critic_tail_args_t;
+typedef struct truss_critic_tail_bwd {
+  size_t struct_size;
+  int32_t n_batch, n_nodes, n_layers, n_hidden, n_q;
+  int32_t dq_stride;             /* floats between the samples of dq, >= 0 (0: one value for every sample) */
+  const float *dq;
+  const float *p, *z1, *z2;
+  const float *w1, *w2, *w3;
+  const float *o[TRUSS_CRITIC_TAIL_MAX_LAYERS];   /* NULL, or what the forward pooled: never read, only held against the outputs */
+  float *d_o[TRUSS_CRITIC_TAIL_MAX_LAYERS];
+  float *dz1, *dz2;
+  float *d_w1, *d_b1, *d_w2, *d_b2, *d_w3, *d_b3;
+} truss_critic_tail_bwd_t;
+int truss_critic_tail(const truss_critic_tail_args_t *items, int32_t n_items, void *stream);
+int truss_critic_tail_backward(const truss_critic_tail_bwd_t *items, int32_t n_items, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

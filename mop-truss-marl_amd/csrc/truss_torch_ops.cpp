@@ -44,7 +44,9 @@
   X(gcn_layer_group, truss_gcn_layer_group, false)               \
   X(pair_setup, truss_pair_setup, false)                         \
   X(gcn_level_aggregate, truss_gcn_level_aggregate, false)        \
-  X(optim_step, truss_optim_step, false)
+  X(optim_step, truss_optim_step, false)                         \
+  X(critic_tail, truss_critic_tail, false)                       \
+  X(critic_tail_backward, truss_critic_tail_backward, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -539,6 +541,128 @@ void optim_step(int64_t lib, int64_t stream, int64_t mode, at::TensorList params
   check_rc(b, b.optim_step(&a, (void *)stream), "truss_optim_step");
 }
 
+// the tails of several critic passes (items) in one call: item j pools its n_layers[j] level outputs o [B, N, H] -- the lists of all
+// items one after the other in `o` -- over the nodes, concatenates them and applies relu(w1 . + b1) [Q, L H], relu(w2 . + b2) [Q, Q],
+// w3 . + b3 [1, Q] -> q[j] [B, 1]; p / z1 / z2: empty lists, or per item None or the tensors [B, L H], [B, Q], [B, Q] the backward
+// reads (all three or none) == truss_critic_tail
+void critic_tail(int64_t lib, int64_t stream, at::TensorList o, at::IntArrayRef n_layers, at::TensorList w1, at::TensorList b1, at::TensorList w2,
+                 at::TensorList b2, at::TensorList w3, at::TensorList b3, at::TensorList q, const c10::List<OT> &p, const c10::List<OT> &z1,
+                 const c10::List<OT> &z2) {
+  const Backend &b = backend(lib);
+  need(b.critic_tail, "truss_critic_tail");
+  const size_t J = n_layers.size();
+  auto per_item = [J](const c10::List<OT> &l) { return l.empty() || l.size() == J; };
+  TORCH_CHECK(w1.size() == J && b1.size() == J && w2.size() == J && b2.size() == J && w3.size() == J && b3.size() == J && q.size() == J &&
+                  per_item(p) && per_item(z1) && per_item(z2) && J <= (size_t)INT32_MAX,
+              "truss_mi355: critic_tail takes one entry per item in every list");
+  std::vector<truss_critic_tail_args_t> items(J);
+  size_t pos = 0;
+  for (size_t j = 0; j < J; ++j) {
+    const int64_t L = n_layers[j];
+    TORCH_CHECK(L >= 1 && L <= TRUSS_CRITIC_TAIL_MAX_LAYERS && pos + (size_t)L <= o.size(), "truss_mi355: critic_tail: n_layers[j] must be 1..",
+                TRUSS_CRITIC_TAIL_MAX_LAYERS, " and o must hold the layers of every item");
+    const at::Tensor &o0 = o[pos];
+    TORCH_CHECK(o0.dim() == 3 && w1[j].dim() == 2 && w2[j].dim() == 2, "truss_mi355: critic_tail: o [B, N, H], w1 [Q, L H], w2 [Q, Q]");
+    const int64_t B = o0.size(0), N = o0.size(1), H = o0.size(2), Q = w1[j].size(0);
+    TORCH_CHECK(B <= INT32_MAX && N <= INT32_MAX && H <= INT32_MAX && Q <= INT32_MAX, "truss_mi355: critic_tail: sizes beyond int32");
+    TORCH_CHECK(w1[j].size(1) == L * H && w2[j].size(0) == Q && w2[j].size(1) == Q, "truss_mi355: critic_tail: w1 must be [Q, L H], w2 [Q, Q]");
+    truss_critic_tail_args_t &a = items[j];
+    a = truss_critic_tail_args_t{};
+    a.struct_size = sizeof(truss_critic_tail_args_t);
+    a.n_batch = (int32_t)B, a.n_nodes = (int32_t)N, a.n_layers = (int32_t)L, a.n_hidden = (int32_t)H, a.n_q = (int32_t)Q;
+    for (int64_t i = 0; i < L; ++i) {
+      TORCH_CHECK(o[pos + i].sizes() == o0.sizes(), "truss_mi355: critic_tail: the layers of an item must have one shape [B, N, H]");
+      a.o[i] = ptr<const float>(b, o[pos + i], at::kFloat, "o");
+    }
+    pos += (size_t)L;
+    a.w1 = ptr<const float>(b, w1[j], at::kFloat, "w1");
+    a.b1 = ptr<const float>(b, b1[j], at::kFloat, "b1", Q);
+    a.w2 = ptr<const float>(b, w2[j], at::kFloat, "w2");
+    a.b2 = ptr<const float>(b, b2[j], at::kFloat, "b2", Q);
+    a.w3 = ptr<const float>(b, w3[j], at::kFloat, "w3", Q);
+    a.b3 = ptr<const float>(b, b3[j], at::kFloat, "b3", 1);
+    TORCH_CHECK(b1[j].numel() == Q && b2[j].numel() == Q && w3[j].numel() == Q && b3[j].numel() == 1 && q[j].numel() == B,
+                "truss_mi355: critic_tail: b1, b2, w3 must hold Q elements, b3 one, q B");
+    a.q = ptr<float>(b, q[j], at::kFloat, "q");
+    const OT pj = at_or_none(p, j), z1j = at_or_none(z1, j), z2j = at_or_none(z2, j);
+    TORCH_CHECK(present(pj) == present(z1j) && present(pj) == present(z2j), "truss_mi355: critic_tail: p, z1 and z2 of an item come together");
+    if (present(pj)) {
+      TORCH_CHECK(pj->numel() == B * L * H && z1j->numel() == B * Q && z2j->numel() == B * Q,
+                  "truss_mi355: critic_tail: p must hold B L H elements, z1 and z2 B Q");
+      a.save = 1;
+      a.p = ptr<float>(b, pj, at::kFloat, "p");
+      a.z1 = ptr<float>(b, z1j, at::kFloat, "z1");
+      a.z2 = ptr<float>(b, z2j, at::kFloat, "z2");
+    }
+  }
+  TORCH_CHECK(pos == o.size(), "truss_mi355: critic_tail: o holds ", o.size(), " tensors, n_layers asks for ", pos);
+  check_rc(b, b.critic_tail(items.data(), (int32_t)J, (void *)stream), "truss_critic_tail");
+}
+
+float *view_ptr(const Backend &b, const at::Tensor &t, const char *name);   // (below: a tensor that need not be contiguous)
+
+// the backward of such tails: per item dq [B, 1] (of any stride over the samples) and the saved z1, z2 (p: only read for d_w1; o: empty, or
+// what the forward pooled, laid out like d_o: not read, only held against the outputs) -> d_o (the layers of all items one
+// after the other, None: not wanted; an empty list: none at all) and the six parameter gradients (empty lists, or per item None or
+// a tensor of the parameter's size); dz1 / dz2 [B, Q]: scratch of the items with a parameter gradient == truss_critic_tail_backward
+void critic_tail_backward(int64_t lib, int64_t stream, at::IntArrayRef n_layers, at::IntArrayRef n_nodes, at::TensorList dq, const c10::List<OT> &p,
+                          at::TensorList z1, at::TensorList z2, at::TensorList w1, at::TensorList w2, at::TensorList w3, const c10::List<OT> &o, const c10::List<OT> &d_o,
+                          const c10::List<OT> &dz1, const c10::List<OT> &dz2, const c10::List<OT> &d_w1, const c10::List<OT> &d_b1,
+                          const c10::List<OT> &d_w2, const c10::List<OT> &d_b2, const c10::List<OT> &d_w3, const c10::List<OT> &d_b3) {
+  const Backend &b = backend(lib);
+  need(b.critic_tail_backward, "truss_critic_tail_backward");
+  const size_t J = n_layers.size();
+  auto per_item = [J](const c10::List<OT> &l) { return l.empty() || l.size() == J; };
+  TORCH_CHECK(n_nodes.size() == J && dq.size() == J && per_item(p) && z1.size() == J && z2.size() == J && w1.size() == J && w2.size() == J &&
+                  w3.size() == J && per_item(dz1) && per_item(dz2) && per_item(d_w1) && per_item(d_b1) && per_item(d_w2) && per_item(d_b2) &&
+                  per_item(d_w3) && per_item(d_b3) && J <= (size_t)INT32_MAX,
+              "truss_mi355: critic_tail_backward takes one entry per item in every list");
+  std::vector<truss_critic_tail_bwd_t> items(J);
+  size_t pos = 0;
+  for (size_t j = 0; j < J; ++j) {
+    const int64_t L = n_layers[j], N = n_nodes[j];
+    TORCH_CHECK(L >= 1 && L <= TRUSS_CRITIC_TAIL_MAX_LAYERS && (d_o.empty() || pos + (size_t)L <= d_o.size()) &&
+                    (o.empty() || pos + (size_t)L <= o.size()),
+                "truss_mi355: critic_tail_backward: n_layers[j] must be 1..", TRUSS_CRITIC_TAIL_MAX_LAYERS, " and d_o empty or one entry per layer");
+    TORCH_CHECK(z1[j].dim() == 2 && w1[j].dim() == 2 && w2[j].dim() == 2, "truss_mi355: critic_tail_backward: z1 [B, Q], w1 [Q, L H], w2 [Q, Q]");
+    const int64_t B = z1[j].size(0), Q = z1[j].size(1), K1 = w1[j].size(1), H = K1 / L;
+    TORCH_CHECK(B <= INT32_MAX && N >= 1 && N <= INT32_MAX && K1 <= INT32_MAX && Q <= INT32_MAX, "truss_mi355: critic_tail_backward: sizes beyond int32");
+    TORCH_CHECK(H * L == K1 && w1[j].size(0) == Q && w2[j].size(0) == Q && w2[j].size(1) == Q && w3[j].numel() == Q && dq[j].numel() == B &&
+                    z2[j].numel() == B * Q,
+                "truss_mi355: critic_tail_backward: dq [B], z1 / z2 [B, Q], w1 [Q, L H], w2 [Q, Q], w3 [Q]");
+    truss_critic_tail_bwd_t &a = items[j];
+    a = truss_critic_tail_bwd_t{};
+    a.struct_size = sizeof(truss_critic_tail_bwd_t);
+    a.n_batch = (int32_t)B, a.n_nodes = (int32_t)N, a.n_layers = (int32_t)L, a.n_hidden = (int32_t)H, a.n_q = (int32_t)Q;
+    TORCH_CHECK((dq[j].dim() == 1 || (dq[j].dim() == 2 && dq[j].size(1) == 1)) && (B <= 1 || (dq[j].stride(0) >= 0 && dq[j].stride(0) <= INT32_MAX)), "truss_mi355: critic_tail_backward: dq must be [B] or [B, 1]");
+    a.dq = view_ptr(b, dq[j], "dq");
+    a.dq_stride = B > 1 ? (int32_t)dq[j].stride(0) : 1;
+    a.p = ptr<const float>(b, at_or_none(p, j), at::kFloat, "p", B * K1);
+    a.z1 = ptr<const float>(b, z1[j], at::kFloat, "z1");
+    a.z2 = ptr<const float>(b, z2[j], at::kFloat, "z2");
+    a.w1 = ptr<const float>(b, w1[j], at::kFloat, "w1");
+    a.w2 = ptr<const float>(b, w2[j], at::kFloat, "w2");
+    a.w3 = ptr<const float>(b, w3[j], at::kFloat, "w3");
+    for (int64_t i = 0; i < L && !o.empty(); ++i) a.o[i] = ptr<const float>(b, o.get(pos + i), at::kFloat, "o", B * N * H);
+    for (int64_t i = 0; i < L && !d_o.empty(); ++i) {
+      const OT d = d_o.get(pos + i);
+      TORCH_CHECK(!present(d) || d->numel() == B * N * H, "truss_mi355: critic_tail_backward: d_o[i] must hold B N H elements");
+      a.d_o[i] = ptr<float>(b, d, at::kFloat, "d_o");
+    }
+    pos += (size_t)L;
+    auto out = [&](const c10::List<OT> &l, int64_t numel, const char *name) {
+      const OT t = at_or_none(l, j);
+      TORCH_CHECK(!present(t) || t->numel() == numel, "truss_mi355: critic_tail_backward: ", name, " must hold ", numel, " elements");
+      return ptr<float>(b, t, at::kFloat, name);
+    };
+    a.dz1 = out(dz1, B * Q, "dz1"), a.dz2 = out(dz2, B * Q, "dz2");
+    a.d_w1 = out(d_w1, Q * K1, "d_w1"), a.d_b1 = out(d_b1, Q, "d_b1"), a.d_w2 = out(d_w2, Q * Q, "d_w2"), a.d_b2 = out(d_b2, Q, "d_b2");
+    a.d_w3 = out(d_w3, Q, "d_w3"), a.d_b3 = out(d_b3, 1, "d_b3");
+  }
+  TORCH_CHECK(d_o.empty() || pos == d_o.size(), "truss_mi355: critic_tail_backward: d_o holds ", d_o.size(), " entries, n_layers asks for ", pos);
+  check_rc(b, b.critic_tail_backward(items.data(), (int32_t)J, (void *)stream), "truss_critic_tail_backward");
+}
+
 // w [C, K] float32 -> out [3, 224, KP] int16 (bfloat16 bit patterns, zero rows / columns beyond C / K): the exact three-term split of the bf16x3 path == truss_gcn_split_w
 void gcn_split_w(int64_t lib, int64_t stream, const at::Tensor &w, const at::Tensor &out) {
   const Backend &b = backend(lib);
@@ -911,6 +1035,11 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("gcn_level_aggregate(int lib, int stream, Tensor[] x, Tensor[] adj, Tensor[] nbr, Tensor(a!)[] y, bool[] transpose) -> ()");
   m.def("optim_step(int lib, int stream, int mode, Tensor(a!)[] params, Tensor grad, Tensor(b!)? exp_avg, Tensor(c!)? exp_avg_sq, Tensor? step, "
         "float lr, float beta1, float beta2, float eps, Tensor(d!) partials, Tensor(e!)? clipped, Tensor(f!)? norms) -> ()");
+  m.def("critic_tail(int lib, int stream, Tensor[] o, int[] n_layers, Tensor[] w1, Tensor[] b1, Tensor[] w2, Tensor[] b2, Tensor[] w3, Tensor[] b3, "
+        "Tensor(a!)[] q, Tensor(b!)?[] p, Tensor(c!)?[] z1, Tensor(d!)?[] z2) -> ()");
+  m.def("critic_tail_backward(int lib, int stream, int[] n_layers, int[] n_nodes, Tensor[] dq, Tensor?[] p, Tensor[] z1, Tensor[] z2, Tensor[] w1, "
+        "Tensor[] w2, Tensor[] w3, Tensor?[] o, Tensor(a!)?[] d_o, Tensor(b!)?[] dz1, Tensor(c!)?[] dz2, Tensor(d!)?[] d_w1, Tensor(e!)?[] d_b1, "
+        "Tensor(f!)?[] d_w2, Tensor(g!)?[] d_b2, Tensor(h!)?[] d_w3, Tensor(i!)?[] d_b3) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

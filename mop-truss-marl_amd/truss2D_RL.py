@@ -189,6 +189,27 @@ def set_optimizer_step(fn, device_type="cuda"):
         _OPTIMIZER_STEP[device_type] = fn
 
 
+_CRITIC_TAIL = {}          # device type -> hook with .forward(items, save) and .backward(items, states, dqs, needs) (truss_mi355.critic_tail)
+# what a critic's tail may measure to go to the hook: pooled layers, their channels, dense units, concatenated length
+CRITIC_TAIL_MAX_LAYERS, CRITIC_TAIL_MAX_HIDDEN, CRITIC_TAIL_MAX_Q, CRITIC_TAIL_MAX_CONCAT = 16, 256, 256, 4096
+
+
+def set_critic_tail(fn, device_type="cuda"):
+    """Install (or, with None, remove) the fused tail of a critic pass -- the 11 sum pools behind the second level, their
+    concatenation and the three dense layers -- for tensors of `device_type`.  With a hook, `_critic_steps` yields a `_TailRequest`
+    behind its second level instead of evaluating the tail, and `run_networks` serves all requests pending at one step with ONE call
+    (`_CriticTail`).  An item is `(outs, params)`: the L level outputs [B, N, H] and (w1, b1, w2, b2, w3, b3) of dense_1, dense_2 and
+    dense_out.  The hook has two methods:
+      forward(items, save) -> (qs, states): q [B, 1] per item; save[j]: a backward may follow for item j, states[j] is then whatever
+          the hook's backward needs of it (else None: nothing is kept);
+      backward(items, states, dqs, needs) -> [(d_outs, d_params)]: needs[j] = (one bool per level output, one per parameter), the
+          gradients in the same order with None where needs says False; dqs[j] [B, 1], of any strides."""
+    if fn is None:
+        _CRITIC_TAIL.pop(device_type, None)
+    else:
+        _CRITIC_TAIL[device_type] = fn
+
+
 # The fused level kernels own whole graphs in a 128-row tile, their dense adjacency included: that envelope ends at 64 nodes
 # (csrc/truss_gcn_level.h, truss_gcn_level_bwd.h).  Above it a level falls to the batched library GEMMs below, which treat the
 # adjacency as a dense N x N matrix although a truss node has at most 9 neighbours -- unless a node table is current
@@ -532,6 +553,9 @@ def _critic_steps(c, inputs, frozen=False):
     xs = [o[0], o[1], o[1], o[2]] + list(o[4:10]) + [x_1_4]
     adjs = [A_n, A_n_ts, A_n_cs, A_s] + [A_n] * 7
     o = yield [(f(c.l2[i]), xs[i], adjs[i], "relu") for i in range(11)]
+    if o[0].device.type in _CRITIC_TAIL and _tail_fits(o, c):      # (`set_critic_tail`: the rest of this pass is the hook's)
+        q = yield _TailRequest(o, (c.dense_1, c.dense_2, c.dense_out), frozen)
+        return q
     # 11 x GlobalSumPool -> Concatenate, as one reduction: [B, 11, N, C] summed over the nodes = the 11 pooled vectors side by side
     q = torch.stack(o, dim=1).sum(dim=2).flatten(1)
     dense = (lambda m, t: nn.functional.linear(t, m.weight.detach(), m.bias.detach())) if frozen else (lambda m, t: m(t))
@@ -540,17 +564,88 @@ def _critic_steps(c, inputs, frozen=False):
     return dense(c.dense_out, q)
 
 
+class _TailRequest:
+    """what `_critic_steps` yields behind its second level where `set_critic_tail` installed a hook: the level's outputs, the three
+    dense modules and whether the pass is frozen (its dense parameters are then seen detached, like its layers)"""
+    __slots__ = ("outs", "dense", "frozen")
+
+    def __init__(self, outs, dense, frozen):
+        self.outs, self.dense, self.frozen = list(outs), dense, frozen
+
+    def params(self):
+        ps = [t for m in self.dense for t in (m.weight, m.bias)]
+        return [t.detach() for t in ps] if self.frozen else ps
+
+
+def _tail_fits(o, c):
+    """the tail of critic `c` behind the level outputs `o` is inside the hook's envelope"""
+    H, Q = o[0].shape[-1], c.dense_1.out_features
+    return (len(o) <= CRITIC_TAIL_MAX_LAYERS and H <= CRITIC_TAIL_MAX_HIDDEN and Q <= CRITIC_TAIL_MAX_Q and len(o) * H <= CRITIC_TAIL_MAX_CONCAT
+            and c.dense_2.out_features == Q and c.dense_out.out_features == 1
+            and all(t.dim() == 3 and t.shape == o[0].shape and t.dtype == torch.float32 for t in o))
+
+
+class _CriticTail(torch.autograd.Function):
+    """The tails of several critic passes as ONE operation (the hook of `set_critic_tail`): inputs, per item, its level outputs and its
+    six dense parameters; outputs, q [B, 1] per item.  The backward asks the hook for exactly what `needs_input_grad` names: a level
+    output nobody differentiates, or the parameters of a frozen pass, get no gradient and cost nothing.  Without a gradient to come
+    (no_grad, or nothing that requires one) nothing is saved."""
+
+    @staticmethod
+    def _split(counts, flat):
+        items, pos = [], 0
+        for L in counts:
+            items.append((list(flat[pos:pos + L]), list(flat[pos + L:pos + L + 6])))
+            pos += L + 6
+        return items
+
+    @staticmethod
+    def forward(ctx, hook, plan, *tensors):
+        counts, live = plan                    # live: gradients are being recorded (needs_input_grad does not know about no_grad)
+        items = _CriticTail._split(counts, tensors)
+        needs = _CriticTail._split(counts, [n and live for n in ctx.needs_input_grad[2:]])
+        qs, states = hook.forward(items, [any(a) or any(b) for a, b in needs])
+        ctx.hook, ctx.counts, ctx.needs, ctx.states = hook, counts, needs, states
+        if any(s is not None for s in states):
+            ctx.save_for_backward(*tensors)
+        return tuple(qs)
+
+    @staticmethod
+    def backward(ctx, *dqs):
+        items = _CriticTail._split(ctx.counts, ctx.saved_tensors)
+        live = [j for j, s in enumerate(ctx.states) if s is not None and dqs[j] is not None]
+        got = ctx.hook.backward([items[j] for j in live], [ctx.states[j] for j in live], [dqs[j] for j in live], [ctx.needs[j] for j in live])
+        grads = [(([None] * L), [None] * 6) for L in ctx.counts]
+        for j, g in zip(live, got):
+            grads[j] = g
+        return (None, None) + tuple(t for d_outs, d_params in grads for t in list(d_outs) + list(d_params))
+
+
+def critic_tail(requests):
+    """the tails of `requests` (`_TailRequest`s on one device) through the hook of `set_critic_tail` -> [q [B, 1]]"""
+    hook = _CRITIC_TAIL[requests[0].outs[0].device.type]
+    flat = [t for r in requests for t in r.outs + r.params()]
+    return list(_CriticTail.apply(hook, (tuple(len(r.outs) for r in requests), torch.is_grad_enabled()), *flat))
+
+
 def run_networks(gens, cache=None):
-    """Step the network generators in lockstep: level k of all of them is ONE `gcn_level`.  Returns their return values."""
+    """Step the network generators in lockstep: level k of all of them is ONE `gcn_level` (and, with `set_critic_tail`, the tails of
+    all critics that have reached theirs ONE `critic_tail`).  Returns their return values."""
     reqs = [next(g) for g in gens]
     results = [None] * len(gens)
     live = list(range(len(gens)))
     while live:
-        outs = gcn_level([r for k in live for r in reqs[k]], cache)
+        tails = [k for k in live if isinstance(reqs[k], _TailRequest)]
+        served = dict(zip(tails, critic_tail([reqs[k] for k in tails]))) if tails else {}
+        levels = [k for k in live if k not in served]
+        outs = gcn_level([r for k in levels for r in reqs[k]], cache) if levels else []
         pos, still = 0, []
         for k in live:
-            o = outs[pos:pos + len(reqs[k])]
-            pos += len(reqs[k])
+            if k in served:
+                o = served[k]
+            else:
+                o = outs[pos:pos + len(reqs[k])]
+                pos += len(reqs[k])
             try:
                 reqs[k] = gens[k].send(o)
                 still.append(k)

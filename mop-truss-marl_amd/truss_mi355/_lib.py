@@ -115,6 +115,29 @@ OPTIM_CHUNK = 4096                    # ... elements per workgroup: `partials` h
 OPTIM_MAX_TENSORS = 160               # ... tensors per launch pair
 
 
+class CriticTailArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_size_t), ("n_batch", C.c_int32), ("n_nodes", C.c_int32), ("n_layers", C.c_int32), ("n_hidden", C.c_int32),
+        ("n_q", C.c_int32), ("save", C.c_int32), ("o", _vp * 16), ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w3", _vp),
+        ("b3", _vp), ("q", _vp), ("p", _vp), ("z1", _vp), ("z2", _vp),
+    ]
+
+
+class CriticTailBwd(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_size_t), ("n_batch", C.c_int32), ("n_nodes", C.c_int32), ("n_layers", C.c_int32), ("n_hidden", C.c_int32),
+        ("n_q", C.c_int32), ("dq_stride", C.c_int32), ("dq", _vp), ("p", _vp), ("z1", _vp), ("z2", _vp), ("w1", _vp), ("w2", _vp),
+        ("w3", _vp), ("o", _vp * 16), ("d_o", _vp * 16), ("dz1", _vp), ("dz2", _vp), ("d_w1", _vp), ("d_b1", _vp), ("d_w2", _vp), ("d_b2", _vp),
+        ("d_w3", _vp), ("d_b3", _vp),
+    ]
+
+
+CRITIC_TAIL_MAX = 4                   # truss_critic_tail: items per launch
+CRITIC_TAIL_MAX_LAYERS = 16           # ... the envelope: layers, channels, dense units, concatenated length
+CRITIC_TAIL_MAX_HIDDEN = CRITIC_TAIL_MAX_Q = 256
+CRITIC_TAIL_MAX_CONCAT = 4096
+
+
 _i32, _i64 = C.c_int32, C.c_int64
 _STRING_GETTERS = ("truss_last_error", "truss_backend")       # return const char *; every other entry returns int
 # THE table of the C ABI (with _LATER_ENTRIES below, which see): (symbol, argtypes, optional).  A library may lack the optional entries (the CPU lane emulator does);
@@ -156,6 +179,8 @@ _LATER_ENTRIES = [
     ("truss_gcn_level_aggregate", [_vp, _i32, _vp]),
     ("truss_optim_step", [C.POINTER(OptimArgs), _vp]),
     ("truss_topo_lds_info", [_vp, _i32, _vp, _vp, _i32, _vp, _i32]),
+    ("truss_critic_tail", [C.POINTER(CriticTailArgs), _i32, _vp]),
+    ("truss_critic_tail_backward", [C.POINTER(CriticTailBwd), _i32, _vp]),
 ]
 
 
@@ -195,6 +220,7 @@ class TrussLib:
         self.has_pair_setup = "truss_pair_setup" in found                                    # the fused set-up of a chunk of pairs
         self.has_level_aggregate = "truss_gcn_level_aggregate" in found                      # a level's neighbour sums through the node table
         self.has_optim_step = "truss_optim_step" in found                                    # clip and Adam of the update as one call
+        self.has_critic_tail = {"truss_critic_tail", "truss_critic_tail_backward"} <= found  # pools and dense layers of a critic pass
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")
         self.backend = d.truss_backend().decode()

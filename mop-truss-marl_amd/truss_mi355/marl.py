@@ -57,6 +57,7 @@ from . import reward as RW
 from .batched import BatchedTruss
 from .gcn import (PRECISIONS, actor_infer, actors_infer, gcn_aggregate, gcn_layer, gcn_layer_group, gcn_layer_head, gcn_layer_pool,  # noqa: F401
                   level_aggregate, level_backward, level_forward, refresh_actor_caches, split_weights)
+from .critic_tail import tail_hook
 from .optim import optimizer_step
 from .pairs import design_coins, pair_dtab, pair_frac_tab, pair_setup, pareto_graph, path_graph_table  # noqa: F401
 from .replay import DeviceReplay
@@ -151,14 +152,20 @@ class BatchedMARL:
     launches, the default) or "hip" (one `truss_optim_step` call, two launches, per step: `optim.optimizer_step`; needs
     a library with that entry); None: "hip" if the environment has TRUSS_OPTIMIZER=hip, else "torch".  Installed process-wide for
     cuda tensors like level_backward, and removed again by an engine built with "torch".  The optimiser's state stays with
-    `SharedStepAdam` either way."""
+    `SharedStepAdam` either way.
+    critic_tail: how the update evaluates the end of a critic pass, behind the second GCN level (11 sum pools, their concatenation,
+    three dense layers; nine passes per update) -- "torch" (framework operators and autograd, the default) or "hip" (`truss_critic_tail`
+    / `truss_critic_tail_backward`: one launch forward for all critics that run together, two backward, `critic_tail.tail_hook`; needs
+    a library with those entries); None: "hip" if the environment has TRUSS_CRITIC_TAIL=hip, else "torch".  Installed process-wide for
+    cuda tensors like optimizer_path, and removed again by an engine built with "torch"."""
 
     def __init__(self, topo: TrussTopology, n_envs: int, maddpg, *, max_front: int | None = None, lib=None, device=None,
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
                  pair_capacity: int | None = None, tune_update_gemms: bool = True, game: str = "train", env_ids=None,
                  level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None,
                  archive_path: str | None = None, actor_path: str | None = None, actor_precision: str | None = None,
-                 pair_path: str | None = None, level_adjacency: str | None = None, optimizer_path: str | None = None):
+                 pair_path: str | None = None, level_adjacency: str | None = None, optimizer_path: str | None = None,
+                 critic_tail: str | None = None):
         if game not in ("train", "test"):
             raise ValueError(f"game must be 'train' or 'test', got {game!r}")
         if game == "test" and len(topo.sym_nodes) == 0:
@@ -188,7 +195,7 @@ class BatchedMARL:
             import truss2D_RL
             truss2D_RL.set_level_forward(level_forward(self.lib), "cuda")   # the update's forward passes: one launch per level
         self._options(level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision, level_adjacency,
-                      optimizer_path)
+                      optimizer_path, critic_tail)
         self._arch_spare = None       # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
         self._pair_dtab = self._pair_frac = None   # pair_path="hip": deg^-1/2 and n / P as the framework rounds them on this device
         #                                             (pair_dtab, pair_frac_tab; made at the first step)
@@ -196,6 +203,7 @@ class BatchedMARL:
             import truss2D_RL
             truss2D_RL.set_level_backward(_level_backward_hook(self.lib) if self.level_backward == "hip" else None, "cuda")
             truss2D_RL.set_optimizer_step(optimizer_step(self.lib) if self.optimizer_path == "hip" else None, "cuda")
+            truss2D_RL.set_critic_tail(tail_hook(self.lib) if self.critic_tail == "hip" else None, "cuda")
         # level_adjacency="table": the node table of this truss, current during every update of this engine (`_train`); the table's
         # device tensor stays with the pattern, i.e. with the engine: a captured update holds its address
         self.pattern = None
@@ -232,7 +240,7 @@ class BatchedMARL:
         self.profile = None            # set to {} to accumulate synchronised wall time per segment (diagnostic)
 
     def _options(self, level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision, level_adjacency,
-                 optimizer_path=None):
+                 optimizer_path=None, critic_tail=None):
         # (see the class) argument, else environment, else default; then what the choice needs of the library and of max_front
         def lib_has(flag, what, entry):
             if not flag:
@@ -245,6 +253,9 @@ class BatchedMARL:
         self.optimizer_path = _option("optimizer_path", optimizer_path, "TRUSS_OPTIMIZER", ("torch", "hip"))
         if self.optimizer_path == "hip":
             lib_has(self.lib.has_optim_step, "optimizer_path='hip'", "truss_optim_step")
+        self.critic_tail = _option("critic_tail", critic_tail, "TRUSS_CRITIC_TAIL", ("torch", "hip"))
+        if self.critic_tail == "hip":
+            lib_has(self.lib.has_critic_tail, "critic_tail='hip'", "truss_critic_tail")
         self.replay_storage = _option("replay_storage", replay_storage, "TRUSS_REPLAY_STORAGE", ("dense", "compact"))
         self.reward_path = _option("reward_path", reward_path, "TRUSS_REWARD", ("torch", "hip"))
         if self.reward_path == "hip":
