@@ -40,6 +40,9 @@
 #ifndef TB_SCHED_FENCE
 #define TB_SCHED_FENCE()  // device: __builtin_amdgcn_sched_barrier(0); pins hand-placed prefetches
 #endif
+#ifndef TB_ARGS_FIRST
+#define TB_ARGS_FIRST(...)  // device: the listed kernel arguments are fetched as one batch of scalar loads and waited for here
+#endif
 #ifndef TRUSS_HD
 #error "define TRUSS_HD (e.g. __device__ __forceinline__) before including truss_body.h"
 #endif
@@ -379,7 +382,62 @@ struct StepLane {
   }
 
   // BI = 16-byte blob units per lane (unrolled): every iteration is a global load and an LDS store for the
-  // whole wave whether or not the blob reaches that far, so the common small blob gets its own instance
+  // whole wave whether or not the blob reaches that far, so the common small blob gets its own instance.
+  // The fast path in two halves, the registers in between: every load (needs lane, g, envc and the kernel arguments, nothing
+  // of init()), and every LDS store.
+  template <int BI>
+  struct StageRegs {
+    tb_u4 vb[BI], vy[NIT], vx[NIT], vt[NIT], vs[EIT], vp[1], vg[2 * NIT], va[3 * NIT];
+    int cb;
+  };
+  template <int BI>
+  TRUSS_HD void stage_fast_load(const TopoDev &T, const StepArgsDev &A, bool decode, StageRegs<BI> &r) const {
+    const size_t bn = (size_t)envc * T.N, be = (size_t)envc * T.E;
+    const int nb = T.blob_bytes >> 4, nn = T.N >> 2, ne = T.E >> 2;
+    {
+      const tb_u4 *s4 = (const tb_u4 *)T.blob;
+#pragma unroll
+      for (int i = 0; i < BI; ++i) {
+        int q = lane + 64 * i;
+        r.vb[i] = s4[q < nb ? q : nb - 1];
+      }
+    }
+    row_load<NIT>(A.y_in + bn, nn, r.vy);
+    row_load<NIT>(A.x + bn, nn, r.vx);
+    row_load<NIT>(A.target + bn, nn, r.vt);
+    row_load<EIT>(A.sec_in + be, ne, r.vs);
+    row_load<1>(A.env_params + (size_t)envc * 8, 4, r.vp);
+    if (decode) {
+      row_load<2 * NIT>(A.a_geo + bn * 2, 2 * nn, r.vg);
+      row_load<3 * NIT>(A.a_topo + bn * 3, 3 * nn, r.va);
+    }
+    r.cb = 0;
+    if (coin_used(T, A)) r.cb = A.coin[envc];   // in flight with the rows (envc is clamped); first used by the LDS store
+  }
+  template <int BI>
+  TRUSS_HD void stage_fast_store(const TopoDev &T, const StepArgsDev &A, bool decode, const StageRegs<BI> &r) {
+    const int nb = T.blob_bytes >> 4, nn = T.N >> 2, ne = T.E >> 2;
+    {
+      tb_u4 *d4 = (tb_u4 *)TB;
+#pragma unroll
+      for (int i = 0; i < BI; ++i) {
+        int q = lane + 64 * i;
+        d4[q < nb ? q : nb - 1] = r.vb[i];
+      }
+    }
+    row_store<NIT>(ysh(T), nn, r.vy);
+    row_store<NIT>(xsh(T), nn, r.vx);
+    row_store<NIT>(tgsh(T), nn, r.vt);
+    row_store<EIT>(secsh(T), ne, r.vs);
+    row_store<1>(par(T), 4, r.vp);
+    if (decode) {
+      row_store<2 * NIT>(geosh(T), 2 * nn, r.vg);
+      row_store<3 * NIT>(tac(T), 3 * nn, r.va);
+    }
+    if (coin_used(T, A)) *coinsh(T) = r.cb;     // every lane of the env stores the same word
+  }
+  // (the two halves in one piece, with local registers: the text every variant without the early issue has always compiled --
+  // <8,8,1,5,EMIT> answered a rewrite in terms of the halves with 36 bytes of scratch)
   template <int BI>
   TRUSS_HD void stage_fast(const TopoDev &T, const StepArgsDev &A, bool decode) {
     const size_t bn = (size_t)envc * T.N, be = (size_t)envc * T.E;
@@ -427,8 +485,60 @@ struct StepLane {
       if (coin) *coinsh(T) = cb;     // every lane of the env stores the same word
     }
   }
+  TRUSS_HD static bool stage_is_fast(const TopoDev &T) {
+    return (T.N & 3) == 0 && (T.E & 3) == 0 && T.N <= NCAP && T.E <= ECAP && T.blob_bytes <= BIT_BIG * 64 * 16;
+  }
+
+  // The loads of the common fast path (blobs of up to PRE_BI units per lane) issued AHEAD of the phase schedule, before init():
+  // a launch is one wave per SIMD, and what it waits for first is its kernel arguments.  Everything the row addresses and
+  // the band clear are computed from is read here as ONE batch of scalar loads (TB_ARGS_FIRST waits for all of them at once),
+  // the loads go out, and the remaining hundred-odd argument words are fetched behind them, under the HBM trip -- the caller
+  // puts a TB_SCHED_FENCE() behind this call.  phase_stage then only clears the band and stores what has landed (pre_issued).
+  // Never called by the emulator nor by the rollout kernel (with it, that kernel's steps measured 0.3 % slower and its first
+  // step no faster: profiles/r21/README.md): phase_stage stages everything itself then.
+  // Only in the step kernels of the metric configuration (<16,8,1,5> and its EMIT twin), where it is measured.  The
+  // 16-wide windows (<16,16,1,5>, <16,8,2,5>) answered it with 36 bytes of scratch per lane, and other 8-wide variants with
+  // AGPRs (<8,8,1,5>: 214 VGPRs + 0 -> 256 + 64), which puts v_accvgpr_read on the pivot chain; nothing was measured there.
+  // Every other variant stages inside phase_stage and reads its arguments as before (profiles/r21/README.md).
+  static constexpr bool PRE = G == 16 && WL == 8 && RPL == 1 && EPL == 5;
+  static constexpr int PRE_BI = 3;
+  StageRegs<PRE_BI> pre_r;
+  int pre_issued = 0;   // 1: pre_r holds the rows
+  TRUSS_HD void stage_issue(int lane_, int block, const TopoDev &T, const StepArgsDev &A) {
+    if constexpr (!PRE) return;
+    // (the last five are wanted for their 64-byte lines only: with them the batch touches every line of the kernel arguments,
+    // and what is fetched behind the row loads hits the scalar cache instead of making a trip of its own, one after the other.
+    // o_zs: neighbours are fetched with one wide load; a word of it that nobody wants is a free register to the allocator, the
+    // next load's destination, and the hardware returns scalar loads in any order: a wait in the middle of the batch.)
+    TB_ARGS_FIRST(T.N, T.E, T.blob_bytes, T.n_sym_nodes, A.B, A.flags, T.blob, A.y_in, A.x, A.target, A.sec_in, A.env_params, A.a_geo,
+                  A.a_topo, A.coin, T.o_env0, T.env_stride, T.o_kb, T.o_zs, T.rowsA, T.rowsB, T.o_par, T.emit_ok, A.mu_out, A.disp64,
+                  A.nxe);
+    lane = lane_;
+    g = lane % G;
+    const int e = block * EPB + lane / G;
+    envc = e < A.B ? e : A.B - 1;
+    if (stage_is_fast(T) && T.blob_bytes <= PRE_BI * 64 * 16) {   // wave-uniform
+      stage_fast_load<PRE_BI>(T, A, !(A.flags & TB_NO_DECODE), pre_r);
+      pre_issued = 1;
+    }
+  }
+
+  // behind stage_issue and the caller's fence: what init(), the band clear and the LDS stores of the rows are computed from, as
+  // one batch again (scalar-cache hits) -- left to the compiler they came in three or four dependent steps
+  TRUSS_HD static void stage_args_second(const TopoDev &T, const StepArgsDev &A) {
+    if constexpr (!PRE) return;
+    TB_ARGS_FIRST(T.N, T.E, T.blob_bytes, T.n_sym_nodes, T.nteams, T.rowsA, T.rowsB, T.zlen, T.o_env0, T.env_stride, T.o_kb, T.o_zs,
+                  T.o_zring, T.o_par, T.o_y, T.o_x, T.o_tg, T.o_geo, T.o_tac, T.o_sec, A.B, A.flags, A.coin, A.y_out, A.sec_out);
+  }
 
   TRUSS_HD void phase_stage(const TopoDev &T, const StepArgsDev &A) {
+    if constexpr (PRE) {
+      if (pre_issued) {   // stage_issue: the rows are in registers or on their way
+        band_clear(T);    // independent of the loads in flight, as in stage_fast
+        stage_fast_store<PRE_BI>(T, A, !(A.flags & TB_NO_DECODE), pre_r);
+        return;
+      }
+    }
     const size_t bn = (size_t)envc * T.N, be = (size_t)envc * T.E;
     const bool decode = !(A.flags & TB_NO_DECODE);
     const bool fast = (T.N & 3) == 0 && (T.E & 3) == 0 && T.N <= NCAP && T.E <= ECAP && T.blob_bytes <= BIT_BIG * 64 * 16;

@@ -33,6 +33,29 @@ __device__ __forceinline__ int tb_opaque(int x) {
   return x;
 }
 #define TB_OPAQUE(x) tb_opaque(x)
+// Kernel arguments that are wanted together: their scalar loads are issued (the arguments are read before the fence, and no
+// load sinks below it), then every value is pinned in a scalar register, which is where the one s_waitcnt for all of them lands.
+template <class V>
+__device__ __forceinline__ void tb_pin_scalar(V v) {
+  asm volatile("" : : "s"(v));
+}
+template <class... Vs>
+__device__ __forceinline__ void tb_args_first(Vs... v) {
+  TB_SCHED_FENCE();
+  (tb_pin_scalar(v), ...);
+  TB_SCHED_FENCE();
+}
+#define TB_ARGS_FIRST(...) tb_args_first(__VA_ARGS__)
+// The kernel arguments through a pointer the optimiser cannot see through, in the constant address space (through a generic
+// pointer the reads became flat_load's).  What is read through it is read behind this point, and no load or store crosses it:
+// the step kernels of the metric configuration fetch everything but the staging's own arguments behind the row loads this way
+// (StepLane::stage_issue).
+typedef const char __attribute__((address_space(4))) *tb_kernarg_ptr;
+__device__ __forceinline__ tb_kernarg_ptr tb_kernargs_here() {
+  tb_kernarg_ptr ka = (tb_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka) : : "memory");
+  return ka;
+}
 // result rows are written once and not read again by this launch: streaming (non-temporal) stores leave
 // no dirty lines behind for the end-of-kernel write-back
 #define TB_STREAM_STORE(p, v) __builtin_nontemporal_store((v), (p))
@@ -261,9 +284,23 @@ __device__ __forceinline__ void tb_obs_timeout(LN &ln, char *lds, int o_flag, in
 #define BAR() TB_WAVE_SYNC()
 
 template <int G, int WL, int RPL, int EPL, bool EMIT>
-__global__ __launch_bounds__(EMIT ? 128 : 64) void truss_step_kernel(const TopoDev T, const StepArgsDev A) {
+__global__ __launch_bounds__(EMIT ? 128 : 64) void truss_step_kernel(const TopoDev T_, const StepArgsDev A_) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   StepLane<G, WL, RPL, EPL, EMIT> ln;
+  if (!EMIT || __builtin_amdgcn_readfirstlane(threadIdx.x) < 64) ln.stage_issue(threadIdx.x & 63, blockIdx.x, T_, A_);   // (EMIT: the compute wave)
+  TB_SCHED_FENCE();   // the rows are on their way: every other kernel argument is fetched behind them, under the HBM trip.
+  // (Read from T_ / A_ directly, the optimiser hoists argument loads of the whole kernel to the entry, in front of the row loads,
+  // with a wait of their own.)  The second argument follows the first at its natural alignment.
+  // The launch signature is (TopoDev, StepArgsDev) by value: hip_run passes exactly these two.
+  struct Kernargs { TopoDev T; StepArgsDev A; };
+  constexpr size_t a_off = (sizeof(TopoDev) + 7) & ~(size_t)7;
+  static_assert(alignof(StepArgsDev) == 8 && alignof(TopoDev) == 8 && offsetof(Kernargs, A) == a_off, "kernel-argument layout");
+  constexpr bool PRE = StepLane<G, WL, RPL, EPL, EMIT>::PRE;   // variants without the early issue read T_ / A_ as they always did
+  tb_kernarg_ptr ka = nullptr;
+  if constexpr (PRE) ka = tb_kernargs_here();
+  const TopoDev &T = [&]() -> const TopoDev & { if constexpr (PRE) return *(const TopoDev *)ka; else return T_; }();
+  const StepArgsDev &A = [&]() -> const StepArgsDev & { if constexpr (PRE) return *(const StepArgsDev *)(ka + a_off); else return A_; }();
+  ln.stage_args_second(T, A);
   ln.init(threadIdx.x & 63, blockIdx.x, T, A, smem);
   constexpr int W_ = StepLane<G, WL, RPL, EPL, EMIT>::W;
   constexpr bool EMIT_ = EMIT;
