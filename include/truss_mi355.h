@@ -43,6 +43,15 @@ extern "C" {
                                       _game_modify builds them in the same call (truss2D_ENV.py:497-500).  One
                                       launch where the topology allows it (truss_topo_fused_obs), otherwise the
                                       observation kernel is queued behind the step on the same stream */
+#define TRUSS_F_OBS_COMPACT 0x8u   /* layout of the three node-graph adjacencies that TRUSS_F_EMIT_OBS writes (valid only
+                                      together with it; TRUSS_EINVAL otherwise): A_s, A_n_ts and A_n_cs are [B][N][Kc] rows
+                                      through the topology's neighbour table (truss_topo_neighbors) instead of [B][N][N]:
+                                        Ac[b][i][t] = A[b][i][nbr[i][t]]  where nbr[i][t] >= 0,  +0.0 in the unused slots
+                                      float32, contiguous, Kc exactly the table's width.  Every value is the one the dense
+                                      layout holds in that cell; x_n, nN_x_n and nN_x_e are unchanged.  The same rows are
+                                      what the GCN layer kernels pick through `nbr` and what the compact replay ring holds */
+/* flag of truss_obs_args_t.flags with the same meaning for truss_obs */
+#define TRUSS_OBS_F_COMPACT 0x8u
 
 /* columns of env_params[B][TRUSS_NPARAM] (float64) */
 #define TRUSS_NPARAM 8
@@ -106,6 +115,14 @@ int truss_topo_solver_info(const truss_topo_t *t, int32_t *perm, int32_t *half_b
 /* 1 when truss_step writes the observation tensors from the step's own launch for this topology
  * (TRUSS_F_EMIT_OBS), 0 when it queues the observation kernel behind it.  Same results either way. */
 int truss_topo_fused_obs(const truss_topo_t *t);
+
+/* The topology's neighbour table, built at truss_topo_create from conn: out[N][k_nbr] int16, per node the columns in which a
+ * node-graph adjacency (A_s, A_n_ts, A_n_cs, A_n) can be non-zero -- the node itself and the far ends of its members --
+ * ascending, -1 in the unused slots; k_nbr = the widest row.  It is the table of the compact observation layout
+ * (TRUSS_F_OBS_COMPACT).  Host pointers; out may be NULL (then only *k_nbr is set), cap = entries `out` holds (TRUSS_EINVAL when
+ * fewer than N * k_nbr).  Optional entry: a caller that wants the compact layout checks that it exists and that the table
+ * equals its own before it trusts the layout. */
+int truss_topo_neighbors(const truss_topo_t *t, int16_t *out, int32_t cap, int32_t *k_nbr);
 
 /* LDS layout of the step launches of this topology, for tests and tools.  emit = 0: the plain step and the persistent
  * rollout; 1: the launch that also writes the observations (where truss_topo_fused_obs() is 0 it has none and the plain
@@ -181,7 +198,8 @@ typedef struct truss_step_args {
                          observation tensors of this env were NOT (completely) written by this call */
 
   /* observation tensors of the new design, written with TRUSS_F_EMIT_OBS (needs sec_out and max_up_out /
-   * max_down_out); same contents and layouts as truss_obs_args_t below; any of them may be NULL */
+   * max_down_out); same contents and layouts as truss_obs_args_t below; any of them may be NULL.  With
+   * TRUSS_F_OBS_COMPACT the three [B][N][N] matrices are [B][N][Kc] */
   float *x_n;     /* [B][N][13]  state_data          truss2D_ENV.py:50-102 */
   float *A_s;     /* [B][N][N]                       :86-87 */
   float *A_n_ts;  /* [B][N][N]                       :92-97 */
@@ -211,6 +229,7 @@ int truss_topo_persistent_rollout(const truss_topo_t *t);
  * state_data + state_data_not_norm (truss2D_ENV.py:40-193) for the design/analysis a truss_step
  * just produced.  A_n, mask and nC_e are topology-static and are NOT written per env (the host
  * mirror builds them once).  All outputs float32, any of them may be NULL.
+ * flags: 0, or TRUSS_OBS_F_COMPACT: A_s, A_n_ts and A_n_cs are [B][N][Kc] (see TRUSS_F_OBS_COMPACT).
  */
 typedef struct truss_obs_args {
   size_t struct_size;
@@ -493,9 +512,17 @@ int truss_gcn_aggregate_sparse(const float *adj, int64_t a_batch_stride, const i
  *   out  [n_batch][n_nodes][c_out], rows out_row_stride floats apart (0 = c_out); must not alias x
  *   act  0 none, 1 relu, 2 sigmoid;  accumulate != 0: out += act(...) (the sum of the five second-level layers of the actor)
  * n_nodes <= 256.  Device pointers. */
+#define TRUSS_GCN_ADJ_DENSE 0
+#define TRUSS_GCN_ADJ_COMPACT 1
 typedef struct truss_gcn_layer_args {
   size_t struct_size;
-  int32_t n_batch, n_nodes, k_in, c_out, act, accumulate, k_nbr, reserved;
+  int32_t n_batch, n_nodes, k_in, c_out, act, accumulate, k_nbr;
+  int32_t adj_layout;  /* TRUSS_GCN_ADJ_DENSE (0): adj as above.  TRUSS_GCN_ADJ_COMPACT (1): adj holds the rows of the compact
+                          observation layout (TRUSS_F_OBS_COMPACT) -- [n_nodes][k_nbr] per graph, a_batch_stride = n_nodes * k_nbr
+                          or 0; nbr is required; term t of row i is adj[i * k_nbr + t] instead of adj[i * n_nodes + nbr[i][t]], its
+                          source row still nbr[i][t].  Same coefficients in the same order: the output is bit for bit that of the
+                          dense call.  Every entry that takes this block honours it for the layer's own adjacency (an epilogue's
+                          adj2 stays dense); truss_gcn_level takes dense adjacencies only.  Any other value: TRUSS_EINVAL */
   const float *x;
   int64_t x_row_stride;
   const float *adj;

@@ -58,6 +58,7 @@
 #define TB_NO_DECODE 0x1u
 #define TB_CLAMP_INPLACE 0x2u
 #define TB_EMIT_OBS 0x4u
+#define TB_OBS_COMPACT 0x8u   // A_s / A_n_ts / A_n_cs as [B][N][Kc] rows through the neighbour table (both StepArgsDev and ObsArgsDev flags)
 
 // 16-byte unit of the HBM<->LDS copies: a native vector type (kept in VGPRs; a struct here ended up in scratch)
 #if defined(__clang__)
@@ -149,6 +150,14 @@ struct TopoDev {
                      //   earlier than the records (progress 2)
   int32_t b_nraw;    // per node, 4 floats: loaded, target / y, |dy|, |dy| / max_def >= 1 (features the step holds in no row)
   int32_t b_nna, b_nnb, b_nn8;   // per node: normalised x_n columns (0 1 4 7), (8 9 10 11) as 4-float records, column 12 as floats
+  // ---- layout of the three node-graph matrices ----
+  // mat_stride4: 16-byte chunks per env of each matrix in the tensors an EMIT launch writes -- N N / 4 (dense [N][N]) or N Kc / 4
+  // (compact [N][Kc]).  The layout is a property of the image: the compact image's et_mat / nc_mat describe the N Kc compact cells
+  // (unused slots -> element E, "no edge"), so the lane program is the same for both.
+  int32_t mat_stride4;
+  // neighbour table (TrussTopology.neighbor_table()): int16 [N][k_nbr], ascending columns, the diagonal included, -1 = unused slot.
+  // Lies in the global blob BEHIND blob_bytes: the observation kernel reads it there, the step kernels do not stage it.
+  int32_t f_nbr, k_nbr;
 };
 
 #define TB_TAB(type, base, off) ((const type *)((base) + (off)))
@@ -1664,7 +1673,7 @@ struct StepLane {
       if (!active || !A.A_s) return;
       const int32_t *S = secsh(T);
       const float *VF = TB_TAB(float, TB, T.f_vsf);
-      tb_f4 *o4 = (tb_f4 *)A.A_s + (size_t)env * ((size_t)T.N * T.N / 4);
+      tb_f4 *o4 = (tb_f4 *)A.A_s + (size_t)env * (size_t)T.mat_stride4;
       const int E = T.E;
 #pragma unroll
       for (int b0 = 0; b0 < IM; b0 += KB) {
@@ -1696,7 +1705,7 @@ struct StepLane {
     if constexpr (EMIT) {
       if (!active || (!A.A_ts && !A.A_cs)) return;
       const tb_f2 *R = (const tb_f2 *)((const float *)L + T.b_tc);
-      const size_t nn4 = (size_t)T.N * T.N / 4;
+      const size_t nn4 = (size_t)T.mat_stride4;
       tb_f4 *pt = (tb_f4 *)A.A_ts + env * nn4, *pc = (tb_f4 *)A.A_cs + env * nn4;
 #pragma unroll
       for (int b0 = 0; b0 < IM; b0 += KB) {
@@ -2312,9 +2321,35 @@ struct ObsLane {
     }
     if (role == 2) return;
     const int rows = (r0 + A.tile_rows <= T.N ? A.tile_rows : T.N - r0);
-    const int nn = rows * T.N;                       // floats of this tile
     const float *M = mats(T);
     float *outs[3] = {A.A_s, A.A_ts, A.A_cs};
+    if (A.flags & TB_OBS_COMPACT) {
+      // compact rows [B][N][Kc]: slot t of row i is column nbr[i][t] of the dense tile, an unused slot +0.  The tile's run of
+      // rows * Kc floats is contiguous in the tensor: 16-byte stores where the run's length and address allow it
+      const int Kc = T.k_nbr, nc = rows * Kc;
+      const int16_t *NB = TB_TAB(int16_t, T.blob, T.f_nbr) + (size_t)r0 * Kc;
+#pragma unroll
+      for (int m = 0; m < 3; ++m) {
+        if (!outs[m]) continue;
+        float *o = outs[m] + ((size_t)env * T.N + r0) * Kc;
+        const float *src = M + m * A.tile_rows * T.N;
+        auto cell = [&](int i) {
+          const int j = NB[i];
+          return j >= 0 ? src[(i / Kc) * T.N + j] : 0.0f;
+        };
+        if ((nc & 3) == 0 && ((size_t)o & 15) == 0) {
+          tb_f4 *o4 = (tb_f4 *)o;
+          for (int i = lane; i < nc / 4; i += 64) {
+            const tb_f4 v = {cell(4 * i), cell(4 * i + 1), cell(4 * i + 2), cell(4 * i + 3)};
+            TB_STREAM_STORE(&o4[i], v);
+          }
+        } else {
+          for (int i = lane; i < nc; i += 64) o[i] = cell(i);
+        }
+      }
+      return;
+    }
+    const int nn = rows * T.N;                       // floats of this tile
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
       if (!outs[m]) continue;

@@ -44,6 +44,17 @@ static inline int tb_gcn_layer_check(const truss_gcn_layer_args_t *a, const char
   if (a->nbr ? (a->k_nbr < 1 || a->k_nbr > 16) : a->n_nodes > 64)
     return fail(TRUSS_EUNSUPPORTED, ": a sparsity pattern of 1..16 terms per row, or a dense adjacency of at most 64 nodes");
   if (a->x == a->out) return fail(TRUSS_EINVAL, ": out must not alias x");
+  // adj_layout: 0 dense rows of n_nodes, 1 compact rows of k_nbr (term t of row i at adj[i * k_nbr + t]); the layer kernels only
+  if (a->adj_layout != TRUSS_GCN_ADJ_DENSE && a->adj_layout != TRUSS_GCN_ADJ_COMPACT) return fail(TRUSS_EINVAL, ": adj_layout is 0 (dense) or 1 (compact)");
+  if (a->adj_layout == TRUSS_GCN_ADJ_COMPACT) {
+    if (!a->nbr) return fail(TRUSS_EINVAL, ": a compact adjacency needs its neighbour table (nbr)");
+    if (a->a_batch_stride != 0 && a->a_batch_stride != (int64_t)a->n_nodes * a->k_nbr)
+      return fail(TRUSS_EINVAL, ": a compact adjacency has a_batch_stride n_nodes * k_nbr, or 0");
+    if (level) return fail(TRUSS_EUNSUPPORTED, ": dense adjacencies only");
+#ifndef __HIPCC__
+    return fail(TRUSS_EUNSUPPORTED, ": this backend reads dense adjacencies only");   // the plain loops of the CPU test backend
+#endif
+  }
   return TRUSS_OK;
 }
 
@@ -115,6 +126,7 @@ struct GcnLayerDev {
   int Kn;                                  // terms per row: k_nbr (pattern) or N (dense)
   int GB;                                  // graphs per tile
   int x_vec, w_vec;                        // 16-byte loads allowed (alignment + k_in % 4 == 0)
+  int a_compact, a_row;                    // adj rows hold the Kn terms themselves (adj_layout 1), not N columns; floats per row of adj: Kn / N
 };
 
 #define TG_KS 16                 // K slab
@@ -134,9 +146,10 @@ __device__ __forceinline__ float tg_act(float v, int act) {
 // The first KT terms of row `an` of an adjacency in registers: coefficients cf[], source nodes cj[] (one byte each, n_nodes <= 256;
 // the caller zeroes cj).  adj_row_offset: float offset of the row in adj.  Branch-free, so that the KT table reads and then the KT
 // coefficient reads are in flight together (a dead row / a term past Kn reads entry 0 and is masked afterwards).
+// compact (uniform): the row holds its Kn terms in table order -- term t lies at adj_row_offset + t, its source node is still nbr's.
 template <int KT>
 __device__ __forceinline__ void tg_load_terms(const int16_t *nbr, const float *adj, long adj_row_offset, int an, int Kn, bool alive,
-                                              float (&cf)[KT], uint32_t (&cj)[(KT + 3) / 4]) {
+                                              float (&cf)[KT], uint32_t (&cj)[(KT + 3) / 4], bool compact = false) {
   int jj[KT];
 #pragma unroll
   for (int t = 0; t < KT; ++t) {
@@ -147,7 +160,7 @@ __device__ __forceinline__ void tg_load_terms(const int16_t *nbr, const float *a
 #pragma unroll
   for (int t = 0; t < KT; ++t) {
     const int j = jj[t];
-    const float c = adj[j < 0 ? 0 : adj_row_offset + j];
+    const float c = adj[j < 0 ? 0 : adj_row_offset + (compact ? t : j)];
     cf[t] = j < 0 ? 0.0f : c;
     cj[t >> 2] |= (uint32_t)(j < 0 ? 0 : j) << (8 * (t & 3));            // a missing term re-reads a live row with coefficient 0
   }
@@ -377,13 +390,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
   uint32_t cj[(TG_KREG + 3) / 4] = {};                     // source nodes of the terms, one byte each (n_nodes <= 256)
   const int abase = ((alive ? ag * N : 0)) * TG_LD + ak;   // float offset of the graph's first row (this thread's eight k's) in sXraw
   if (kreg) {
-    tg_load_terms<TG_KREG>(P.nbr, P.adj, (long)(g0 + ag) * P.a_stride + (long)an * N, an, Kn, alive, cf, cj);
+    tg_load_terms<TG_KREG>(P.nbr, P.adj, (long)(g0 + ag) * P.a_stride + (long)an * P.a_row, an, Kn, alive, cf, cj, P.a_compact != 0);
   } else {
     for (int i = tid; i < N * Kn; i += NT) sIdx[i] = P.nbr ? P.nbr[i] : (int16_t)(i % Kn);
     for (int i = tid; i < rows * Kn; i += NT) {
       const int r = i / Kn, t = i - r * Kn, g = r / N, n = r - g * N;
       const int j = P.nbr ? (int)P.nbr[n * Kn + t] : t;
-      sCoef[i] = j < 0 ? 0.0f : P.adj[(long)(g0 + g) * P.a_stride + (long)n * N + j];
+      sCoef[i] = j < 0 ? 0.0f : P.adj[(long)(g0 + g) * P.a_stride + (long)n * P.a_row + (P.a_compact ? t : j)];
     }
   }
 
@@ -693,6 +706,8 @@ static GcnLayerDev tg_layer_dev(const truss_gcn_layer_args_t *a, int tile_rows) 
   P.GB = tile_rows / a->n_nodes;
   P.x_vec = tb_gcn_x_vec(a) ? 1 : 0;
   P.w_vec = ((size_t)a->w % 16 == 0 && a->k_in % 4 == 0) ? 1 : 0;
+  P.a_compact = a->adj_layout == TRUSS_GCN_ADJ_COMPACT ? 1 : 0;
+  P.a_row = P.a_compact ? a->k_nbr : a->n_nodes;
   return P;
 }
 

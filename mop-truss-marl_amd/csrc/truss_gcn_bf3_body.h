@@ -34,7 +34,7 @@
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
       const int j = jj[t];
-      const float c = P.adj[j < 0 ? 0 : (long)(g0 + ag) * P.a_stride + (long)an * N + j];
+      const float c = P.adj[j < 0 ? 0 : (long)(g0 + ag) * P.a_stride + (long)an * P.a_row + (P.a_compact ? t : j)];   // compact rows: term t itself
       cf[t] = j < 0 ? 0.0f : c;
       cj[t >> 2] |= (uint32_t)(j < 0 ? 0 : j) << (8 * (t & 3));
     }

@@ -69,8 +69,9 @@ static bool tgg_hits(const float *p, int64_t n, const truss_gcn_layer_args_t *a,
     const int64_t np = ((int64_t)a->n_batch - 1) * (e->pool_row_stride ? e->pool_row_stride : a->c_out) + a->c_out;
     if (e->kind == TRUSS_GCN_EPI_HEAD ? tb_gcn_overlap(p, n, e->out2, n2) : tb_gcn_overlap(p, n, e->pool, np)) return true;
   }
-  const int64_t nadj = a->a_batch_stride ? ((int64_t)a->n_batch - 1) * a->a_batch_stride + (int64_t)a->n_nodes * a->n_nodes
-                                         : (int64_t)a->n_nodes * a->n_nodes;
+  const int64_t arow = a->adj_layout == TRUSS_GCN_ADJ_COMPACT ? a->k_nbr : a->n_nodes;     // floats per row of adj
+  const int64_t nadj = a->a_batch_stride ? ((int64_t)a->n_batch - 1) * a->a_batch_stride + (int64_t)a->n_nodes * arow
+                                         : (int64_t)a->n_nodes * arow;
   if (tb_gcn_overlap(p, n, a->x, nx) || tb_gcn_overlap(p, n, a->adj, nadj) || tb_gcn_overlap(p, n, a->w, (int64_t)a->c_out * a->k_in) ||
       tb_gcn_overlap(p, n, a->bias, a->c_out))
     return true;

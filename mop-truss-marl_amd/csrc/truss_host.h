@@ -135,6 +135,14 @@ struct truss_topo {
   TopoDev dev{};        // what a plain step launch gets
   TopoDev dev_emit{};   // ... an EMIT launch: the staged tables include the nN_x_e gather table (larger blob_bytes / o_env0)
   size_t lds_bytes_emit = 0;
+  // neighbour table (TrussTopology.neighbor_table()): int16 [N][k_nbr], ascending, the diagonal included, -1 = unused slot
+  std::vector<int16_t> nbr;
+  int k_nbr = 0;
+  // TRUSS_F_OBS_COMPACT on a topology with the fused writer: a twin whose dev_emit is the COMPACT image (matrix table, chunk count
+  // and env stride of the [N][k_nbr] rows; everything else equal to dev_emit).  tb_launch_step gets the twin in place of this
+  // topology, so a backend launches the same kernel with another image and knows nothing of layouts.  The twin owns no memory.
+  std::unique_ptr<truss_topo> compact;
+  int32_t et_mat_c = 0, nc_mat_c = 0;   // the compact image's matrix table in etab and its chunks per env (tb_build_emit)
   void *blob = nullptr;   // device memory, owned: the topology tables (TopoDev::blob) ...
   void *etab = nullptr;   // ... and the emission tables of the fused observation writer (TopoDev::etab)
   size_t lds_bytes = 0;
@@ -237,6 +245,17 @@ static bool tb_build_emit(truss_topo *t, TopoDev &D, const int32_t *conn, const 
   D.nxe_cw = (E & 3) == 0 ? 4 : (E & 1) == 0 ? 2 : 1;    // 21 E floats per env: 16-, 8- or 4-byte aligned rows
   D.nc_nxe = (int32_t)tnxe.size() / D.nxe_cw;
   D.nc_mat = (int32_t)tmat.size() / 4;
+  D.mat_stride4 = D.nc_mat;
+  // the same table over the N Kc cells of the compact rows (TRUSS_F_OBS_COMPACT): slot t of row i is the element joining
+  // (i, nbr[i][t]); the diagonal and the unused slots have none.  N % 4 == 0, so N Kc / 4 is whole.
+  const int Kc = t->k_nbr;
+  std::vector<uint16_t> tmatc((size_t)N * Kc, (uint16_t)E);
+  for (int i = 0; i < N; ++i)
+    for (int s = 0; s < Kc; ++s) {
+      const int j = t->nbr[(size_t)i * Kc + s];
+      if (j >= 0 && j != i) tmatc[(size_t)i * Kc + s] = tmat[(size_t)i * N + j];
+    }
+  t->nc_mat_c = (int32_t)tmatc.size() / 4;
   // pad to `iters` iterations of G chunks (entries past the end repeat the last chunk); chunk q = iteration q / G, lane q % G
   auto padded = [&](const std::vector<uint16_t> &v, int iters) {
     const size_t nc = v.size() / 4;
@@ -259,6 +278,7 @@ static bool tb_build_emit(truss_topo *t, TopoDev &D, const int32_t *conn, const 
   D.et_xn = tb_push(tab, paired(txn, IX));
   D.et_nxn = tb_push(tab, paired(tnxn, IN_));
   D.et_mat = tb_push(tab, paired(tmat, IM));
+  t->et_mat_c = tb_push(tab, paired(tmatc, IM));   // Kc <= N: never more chunks than the dense matrix
   tab.resize((tab.size() + 15) & ~size_t(15));
   t->etab = tb_dev_alloc(tab.size());   // t's from here on, whatever becomes of the upload
   if (!t->etab || !tb_dev_upload(t->etab, tab.data(), tab.size())) return false;
@@ -397,6 +417,26 @@ static bool tb_vertical_pairs(const int32_t *pair, int N, std::vector<int16_t> &
     }
   }
   return true;
+}
+
+// ---- neighbour table: per node the columns in which a node-graph adjacency can be non-zero -- the node itself and the far ends
+// of its members -- ascending, padded with -1 to the widest row (the rule of TrussTopology.neighbor_table()) ----
+static void tb_neighbor_table(const TbInput &in, std::vector<int16_t> &nbr, int &k_nbr) {
+  std::vector<std::vector<int>> cols(in.N);
+  for (int n = 0; n < in.N; ++n) cols[n].push_back(n);
+  for (int e = 0; e < in.E; ++e) {
+    cols[in.conn[2 * e]].push_back(in.conn[2 * e + 1]);
+    cols[in.conn[2 * e + 1]].push_back(in.conn[2 * e]);
+  }
+  k_nbr = 0;
+  for (auto &c : cols) {
+    std::sort(c.begin(), c.end());
+    c.erase(std::unique(c.begin(), c.end()), c.end());
+    k_nbr = std::max(k_nbr, (int)c.size());
+  }
+  nbr.assign((size_t)in.N * k_nbr, (int16_t)-1);
+  for (int n = 0; n < in.N; ++n)
+    for (size_t s = 0; s < cols[n].size(); ++s) nbr[(size_t)n * k_nbr + s] = (int16_t)cols[n][s];
 }
 
 // ---- node ordering for the banded solver: hint, natural, RCM from every start; the first candidate with the smallest
@@ -784,6 +824,7 @@ extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const
   t->N = N;
   t->E = E;
   t->n_sections = n_sections;
+  tb_neighbor_table(in, t->nbr, t->k_nbr);
   tb_dof_numbering(*t, conn, res);
   if (t->ndof < 1) return tb_fail(TRUSS_EINVAL, "no free DOF");
   std::vector<int16_t> pairs;
@@ -813,6 +854,12 @@ extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const
   if (int rc = tb_build_tables(*t, D, g, in, dofpos, pairs, blob, t->band_offsets[0])) return rc;
   std::vector<TbFrag> fr_early, fr_late;
   t->lds_bytes = tb_lds_layout(*t, D, g, blob.size(), fr_early, fr_late, t->layout[0]);
+  // the neighbour table of the observation kernel's compact rows: uploaded with the tables, behind the D.blob_bytes that the step
+  // kernels stage (their LDS layout stands as computed above)
+  D.f_nbr = tb_push(blob, t->nbr);
+  D.k_nbr = t->k_nbr;
+  D.mat_stride4 = N * N / 4;
+  blob.resize((blob.size() + 15) & ~size_t(15));
   if (tb_variant_emits(t->G, t->WL, t->RPL, t->EPL)) {
     if (int rc = tb_build_tables(*t, DE, ge, in, dofpos, pairs, blob_e, t->band_offsets[1])) return rc;
     fr_early.clear();
@@ -840,6 +887,25 @@ extern "C" int truss_topo_create(truss_topo_t **out, int32_t N, int32_t E, const
     t->lds_bytes_emit = t->lds_bytes;
   }
   D.emit_ok = DE.emit_ok;
+  if (DE.emit_ok) {      // the twin of TRUSS_F_OBS_COMPACT launches: what a backend's tb_launch_step reads of a topology
+    truss_topo *c = new truss_topo();
+    t->compact.reset(c);
+    c->N = t->N;
+    c->E = t->E;
+    c->G = t->G;
+    c->WL = t->WL;
+    c->RPL = t->RPL;
+    c->EPL = t->EPL;
+    c->W = t->W;
+    c->variant = t->variant;
+    c->lds_bytes = t->lds_bytes;
+    c->lds_bytes_emit = t->lds_bytes_emit;
+    c->dev = D;
+    c->dev_emit = DE;
+    c->dev_emit.et_mat = t->et_mat_c;
+    c->dev_emit.nc_mat = t->nc_mat_c;
+    c->dev_emit.mat_stride4 = t->nc_mat_c;
+  }
   if (tb_env_int("TRUSS_VERBOSE", 0))
     fprintf(stderr,
             "[truss_mi355] N=%d E=%d ndof=%d bw=%d | G=%d WL=%d RPL=%d EPL=%d teams=%d KA=%d mid=%d | band rows %d B apart, tables %d B, "
@@ -877,6 +943,16 @@ extern "C" int truss_topo_solver_info(const truss_topo_t *t, int32_t *perm, int3
 }
 
 extern "C" int truss_topo_fused_obs(const truss_topo_t *t) { return t && t->dev.emit_ok ? 1 : 0; }
+
+extern "C" int truss_topo_neighbors(const truss_topo_t *t, int16_t *out, int32_t cap, int32_t *k_nbr) {
+  if (!t) return tb_fail(TRUSS_EINVAL, "NULL topology");
+  if (k_nbr) *k_nbr = t->k_nbr;
+  if (out) {
+    if (cap < (int32_t)t->nbr.size()) return tb_fail(TRUSS_EINVAL, "truss_topo_neighbors: out holds fewer than n_nodes * k_nbr entries");
+    memcpy(out, t->nbr.data(), t->nbr.size() * sizeof(int16_t));
+  }
+  return TRUSS_OK;
+}
 
 extern "C" int truss_topo_lds_info(const truss_topo_t *t, int32_t emit, int32_t *info, int32_t *live, int32_t cap_live,
                                    int32_t *band_offsets, int32_t cap_offsets) {
@@ -945,6 +1021,10 @@ static int tb_make_step_args(const truss_topo_t *t, const truss_step_args_t *a, 
   D.A_cs = a->A_n_cs;
   D.nxn = a->nN_x_n;
   D.nxe = a->nN_x_e;
+  if ((a->flags & TRUSS_F_OBS_COMPACT) && !(a->flags & TRUSS_F_EMIT_OBS))
+    return tb_fail(TRUSS_EINVAL, "TRUSS_F_OBS_COMPACT is a layout of TRUSS_F_EMIT_OBS: set both");
+  if ((a->flags & TRUSS_F_OBS_COMPACT) && t->dev.emit_ok && !t->compact)
+    return tb_fail(TRUSS_EUNSUPPORTED, "internal: no compact image for the fused observation writer");
   if (a->flags & TRUSS_F_EMIT_OBS) {
     if (!a->sec_out || !a->max_up_out) return tb_fail(TRUSS_EINVAL, "TRUSS_F_EMIT_OBS needs sec_out and max_up_out / max_down_out");
     if (!t->dev.emit_ok && tb_obs_lds_bytes(t->N) > 160 * 1024) return tb_fail(TRUSS_EUNSUPPORTED, "N too large for the observation kernel");
@@ -964,10 +1044,11 @@ static ObsArgsDev tb_obs_args(int N, ObsArgsDev O) {
 // it (dev.emit_ok) and from the observation kernel, launched right behind the step on the same stream, elsewhere.
 static int tb_step_dispatch(const truss_topo *t, const StepArgsDev &D, void *stream) {
   if (!(D.flags & TB_EMIT_OBS)) return tb_launch_step(t, D, false, stream);
-  if (t->dev.emit_ok) return tb_launch_step(t, D, true, stream);
+  // the layout of the fused writer is a property of the image: a compact launch is the same kernel on the twin's image
+  if (t->dev.emit_ok) return tb_launch_step((D.flags & TB_OBS_COMPACT) ? t->compact.get() : t, D, true, stream);
   int rc = tb_launch_step(t, D, false, stream);
   if (rc != TRUSS_OK) return rc;
-  return tb_launch_obs(t, tb_obs_args(t->N, {D.B, 0, D.x, D.y_out, D.sec_out, D.mu_out, D.md_out, D.target, D.disp, D.q0, D.sr, D.comp,
+  return tb_launch_obs(t, tb_obs_args(t->N, {D.B, D.flags & TB_OBS_COMPACT, D.x, D.y_out, D.sec_out, D.mu_out, D.md_out, D.target, D.disp, D.q0, D.sr, D.comp,
                                              D.env_params, D.x_n, D.A_s, D.A_ts, D.A_cs, D.nxn, D.nxe}), stream);
 }
 

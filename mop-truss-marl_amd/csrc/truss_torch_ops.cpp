@@ -56,6 +56,7 @@ struct Backend {
   TRUSS_ENTRY_POINTS(X)
 #undef X
   bool device = false;   // true: the HIP library (tensors must be on a cuda device)
+  decltype(&truss_topo_neighbors) topo_neighbors = nullptr;   // no operator of its own: the width of the compact observation rows
 };
 std::array<Backend, 8> g_backends;
 
@@ -105,7 +106,16 @@ void need(F fn, const char *symbol) {
   x, y_in, sec_in, max_up_in, max_down_in, a_geo, a_topo, coin, target, env_params, y_out, sec_out, max_up_out, max_down_out,  \
       disp, q0, sr, comp, point, obj, disp_f64, q0_f64, energy, reactions, status, x_n, A_s, A_n_ts, A_n_cs, nN_x_n, nN_x_e
 
-void fill_step(const Backend &b, truss_step_args_t &a, int64_t flags, int64_t n_envs, int64_t N, int64_t E, int64_t sets,
+// floats per env of A_s / A_n_ts / A_n_cs: N N, or N Kc in the compact layout (the library's own table width)
+int64_t adj_floats(const Backend &b, int64_t topo, int64_t N, bool compact) {
+  if (!compact) return N * N;
+  need(b.topo_neighbors, "truss_topo_neighbors");
+  int32_t k = 0;
+  check_rc(b, b.topo_neighbors((const truss_topo_t *)topo, nullptr, 0, &k), "truss_topo_neighbors");
+  return N * (int64_t)k;
+}
+
+void fill_step(const Backend &b, int64_t topo, truss_step_args_t &a, int64_t flags, int64_t n_envs, int64_t N, int64_t E, int64_t sets,
                STEP_TENSOR_PARAMS) {
   TORCH_CHECK(n_envs >= 1 && N >= 2 && E >= 1, "truss_mi355: bad n_envs / n_nodes / n_elems");
   const int64_t B = n_envs, BN = B * N, BE = B * E;
@@ -140,9 +150,10 @@ void fill_step(const Backend &b, truss_step_args_t &a, int64_t flags, int64_t n_
   a.reactions = ptr<double>(b, reactions, f64, "reactions", B);
   a.status = ptr<int32_t>(b, status, i32, "status", B);
   a.x_n = ptr<float>(b, x_n, f32, "x_n", BN * 13);
-  a.A_s = ptr<float>(b, A_s, f32, "A_s", BN * N);
-  a.A_n_ts = ptr<float>(b, A_n_ts, f32, "A_n_ts", BN * N);
-  a.A_n_cs = ptr<float>(b, A_n_cs, f32, "A_n_cs", BN * N);
+  const int64_t BA = B * adj_floats(b, topo, N, (flags & TRUSS_F_OBS_COMPACT) != 0);
+  a.A_s = ptr<float>(b, A_s, f32, "A_s", BA);
+  a.A_n_ts = ptr<float>(b, A_n_ts, f32, "A_n_ts", BA);
+  a.A_n_cs = ptr<float>(b, A_n_cs, f32, "A_n_cs", BA);
   a.nN_x_n = ptr<float>(b, nN_x_n, f32, "nN_x_n", BN * 12);
   a.nN_x_e = ptr<float>(b, nN_x_e, f32, "nN_x_e", BE * 21);
 }
@@ -152,7 +163,7 @@ void step(int64_t lib, int64_t topo, int64_t stream, int64_t flags, int64_t n_en
           STEP_TENSOR_PARAMS) {
   const Backend &b = backend(lib);
   truss_step_args_t a;
-  fill_step(b, a, flags, n_envs, n_nodes, n_elems, 1, STEP_TENSOR_ARGS);
+  fill_step(b, topo, a, flags, n_envs, n_nodes, n_elems, 1, STEP_TENSOR_ARGS);
   check_rc(b, b.step((const truss_topo_t *)topo, &a, (void *)stream), "truss_step");
 }
 // n_steps chained transitions (truss_rollout); a_geo / a_topo hold n_action_sets action sets
@@ -160,12 +171,12 @@ void rollout(int64_t lib, int64_t topo, int64_t stream, int64_t flags, int64_t n
              int64_t n_steps, int64_t n_action_sets, STEP_TENSOR_PARAMS) {
   const Backend &b = backend(lib);
   truss_step_args_t a;
-  fill_step(b, a, flags, n_envs, n_nodes, n_elems, n_action_sets, STEP_TENSOR_ARGS);
+  fill_step(b, topo, a, flags, n_envs, n_nodes, n_elems, n_action_sets, STEP_TENSOR_ARGS);
   check_rc(b, b.rollout((const truss_topo_t *)topo, &a, (int32_t)n_steps, (int32_t)n_action_sets, (void *)stream), "truss_rollout");
 }
 
 // state_data + state_data_not_norm (truss2D_ENV.py:40-193) == truss_obs
-void obs(int64_t lib, int64_t topo, int64_t stream, int64_t n_envs, int64_t N, int64_t E, const at::Tensor &x, const at::Tensor &y,
+void obs_flags(int64_t lib, int64_t topo, int64_t stream, int64_t flags, int64_t n_envs, int64_t N, int64_t E, const at::Tensor &x, const at::Tensor &y,
          const at::Tensor &sec, const at::Tensor &max_up, const at::Tensor &max_down, const at::Tensor &target, const at::Tensor &disp,
          const at::Tensor &q0, const at::Tensor &sr, const at::Tensor &comp, const at::Tensor &env_params, const OT &x_n, const OT &A_s,
          const OT &A_n_ts, const OT &A_n_cs, const OT &nN_x_n, const OT &nN_x_e) {
@@ -176,6 +187,7 @@ void obs(int64_t lib, int64_t topo, int64_t stream, int64_t n_envs, int64_t N, i
   truss_obs_args_t a{};
   a.struct_size = sizeof(truss_obs_args_t);
   a.n_envs = (int32_t)B;
+  a.flags = (uint32_t)flags;
   a.x = ptr<const float>(b, x, f32, "x", BN);
   a.y = ptr<const float>(b, y, f32, "y", BN);
   a.sec = ptr<const int32_t>(b, sec, at::kInt, "sec", BE);
@@ -188,12 +200,21 @@ void obs(int64_t lib, int64_t topo, int64_t stream, int64_t n_envs, int64_t N, i
   a.comp = ptr<const uint8_t>(b, comp, at::kByte, "comp", BE);
   a.env_params = ptr<const double>(b, env_params, at::kDouble, "env_params", B * TRUSS_NPARAM);
   a.x_n = ptr<float>(b, x_n, f32, "x_n", BN * 13);
-  a.A_s = ptr<float>(b, A_s, f32, "A_s", BN * N);
-  a.A_n_ts = ptr<float>(b, A_n_ts, f32, "A_n_ts", BN * N);
-  a.A_n_cs = ptr<float>(b, A_n_cs, f32, "A_n_cs", BN * N);
+  const int64_t BA = B * adj_floats(b, topo, N, (flags & TRUSS_OBS_F_COMPACT) != 0);
+  a.A_s = ptr<float>(b, A_s, f32, "A_s", BA);
+  a.A_n_ts = ptr<float>(b, A_n_ts, f32, "A_n_ts", BA);
+  a.A_n_cs = ptr<float>(b, A_n_cs, f32, "A_n_cs", BA);
   a.nN_x_n = ptr<float>(b, nN_x_n, f32, "nN_x_n", BN * 12);
   a.nN_x_e = ptr<float>(b, nN_x_e, f32, "nN_x_e", BE * 21);
   check_rc(b, b.obs((const truss_topo_t *)topo, &a, (void *)stream), "truss_obs");
+}
+// the same with flags = 0: the dense layout
+void obs(int64_t lib, int64_t topo, int64_t stream, int64_t n_envs, int64_t N, int64_t E, const at::Tensor &x, const at::Tensor &y,
+         const at::Tensor &sec, const at::Tensor &max_up, const at::Tensor &max_down, const at::Tensor &target, const at::Tensor &disp,
+         const at::Tensor &q0, const at::Tensor &sr, const at::Tensor &comp, const at::Tensor &env_params, const OT &x_n, const OT &A_s,
+         const OT &A_n_ts, const OT &A_n_cs, const OT &nN_x_n, const OT &nN_x_e) {
+  obs_flags(lib, topo, stream, 0, n_envs, N, E, x, y, sec, max_up, max_down, target, disp, q0, sr, comp, env_params, x_n, A_s, A_n_ts, A_n_cs,
+            nN_x_n, nN_x_e);
 }
 
 // Pareto cull + 2-D hypervolume of B small point sets (utils.py:11-342) == truss_front
@@ -227,10 +248,21 @@ void check_adj(const at::Tensor &adj, int64_t B, int64_t N) {
 }
 // the argument block of one layer: sizes, activation, x (absent in the backward), the adjacency with its optional sparsity
 // pattern, the weights; bias / out and the rest are the caller's
+// adj_layout 1: adj holds the compact rows [N, Kc] / [B, N, Kc] of its table nbr [N, Kc]; any other value passes with the dense shapes
+// and the library judges it
 truss_gcn_layer_args_t layer_args(const Backend &b, int64_t B, int64_t N, int64_t K, int64_t C, int64_t act, const at::Tensor *x,
-                                  const at::Tensor &adj, const OT &nbr, const at::Tensor &w) {
-  check_adj(adj, B, N);
+                                  const at::Tensor &adj, const OT &nbr, const at::Tensor &w, int64_t adj_layout = 0) {
+  const bool compact = adj_layout == TRUSS_GCN_ADJ_COMPACT;
+  if (compact) {
+    TORCH_CHECK(present(nbr) && nbr->dim() == 2, "truss_mi355: a compact adj needs its table nbr [N, Kc]");
+    TORCH_CHECK((adj.dim() == 2 || adj.dim() == 3) && adj.size(-1) == nbr->size(1) && adj.size(-2) == N && (adj.dim() == 2 || adj.size(0) == B),
+                "truss_mi355: a compact adj must be [N, Kc] or [B, N, Kc] with nbr [N, Kc]");
+  } else {
+    check_adj(adj, B, N);
+  }
+  TORCH_CHECK(adj_layout >= INT32_MIN && adj_layout <= INT32_MAX, "truss_mi355: adj_layout out of range");
   truss_gcn_layer_args_t a{};
+  a.adj_layout = (int32_t)adj_layout;
   a.struct_size = sizeof a;
   a.n_batch = (int32_t)B;
   a.n_nodes = (int32_t)N;
@@ -239,7 +271,7 @@ truss_gcn_layer_args_t layer_args(const Backend &b, int64_t B, int64_t N, int64_
   a.act = (int32_t)act;
   if (x) a.x = ptr<const float>(b, *x, at::kFloat, "x");
   a.adj = ptr<const float>(b, adj, at::kFloat, "adj");
-  a.a_batch_stride = adj.dim() == 3 ? N * N : 0;
+  a.a_batch_stride = adj.dim() == 3 ? N * adj.size(-1) : 0;
   if (present(nbr)) {
     TORCH_CHECK(nbr->dim() == 2 && nbr->size(0) == N, "truss_mi355: nbr must be [N, K]");
     a.nbr = ptr<const int16_t>(b, *nbr, at::kShort, "nbr");
@@ -250,11 +282,11 @@ truss_gcn_layer_args_t layer_args(const Backend &b, int64_t B, int64_t N, int64_
 }
 // the same for a forward layer of operator `op`, from its tensors: shapes checked, bias and out filled in
 truss_gcn_layer_args_t forward_args(const Backend &b, const char *op, const at::Tensor &x, const at::Tensor &adj, const OT &nbr,
-                                    const at::Tensor &w, const OT &bias, const at::Tensor &out, int64_t act) {
+                                    const at::Tensor &w, const OT &bias, const at::Tensor &out, int64_t act, int64_t adj_layout = 0) {
   TORCH_CHECK(x.dim() == 3 && out.dim() == 3 && w.dim() == 2, "truss_mi355: x [B, N, K], w [C, K], out [B, N, C]");
   const int64_t B = x.size(0), N = x.size(1), K = x.size(2), C = w.size(0);
   TORCH_CHECK(w.size(1) == K && out.size(0) == B && out.size(1) == N && out.size(2) == C, "truss_mi355: ", op, " shapes do not match");
-  truss_gcn_layer_args_t a = layer_args(b, B, N, K, C, act, &x, adj, nbr, w);
+  truss_gcn_layer_args_t a = layer_args(b, B, N, K, C, act, &x, adj, nbr, w, adj_layout);
   a.bias = ptr<const float>(b, bias, at::kFloat, "bias", C);
   a.out = ptr<float>(b, out, at::kFloat, "out");
   return a;
@@ -295,9 +327,9 @@ void gcn_aggregate_sparse(int64_t lib, int64_t stream, const at::Tensor &adj, co
 
 // one whole GCN layer, out = act(adj @ (x @ w^T) + bias) [+ out], on the matrix cores == truss_gcn_layer
 void gcn_layer(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
-               const at::Tensor &out, int64_t act, bool accumulate, const OT &w_split) {
+               const at::Tensor &out, int64_t act, bool accumulate, const OT &w_split, int64_t adj_layout) {
   const Backend &b = backend(lib);
-  truss_gcn_layer_args_t a = forward_args(b, "gcn_layer", x, adj, nbr, w, bias, out, act);
+  truss_gcn_layer_args_t a = forward_args(b, "gcn_layer", x, adj, nbr, w, bias, out, act, adj_layout);
   a.accumulate = accumulate ? 1 : 0;
   a.w_bf16x3 = (const uint16_t *)ptr<const int16_t>(b, w_split, at::kShort, "w_split", 3 * 224 * ((a.k_in + 15) / 16 * 16));
   check_rc(b, b.gcn_layer(&a, (void *)stream), "truss_gcn_layer");
@@ -308,10 +340,10 @@ void gcn_layer(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tenso
 // (the argument blocks of the two operators that take an epilogue)
 void fused_args(const Backend &b, truss_gcn_layer_args_t &a, truss_gcn_epilogue_t &e, const at::Tensor &x, const at::Tensor &adj, const OT &nbr,
                 const at::Tensor &w, const OT &bias, const OT &out, int64_t act, const OT &w_split, int64_t kind, const OT &w2, const OT &bias2,
-                const OT &adj2, const OT &nbr2, int64_t act2, const OT &out2, const OT &pool) {
+                const OT &adj2, const OT &nbr2, int64_t act2, const OT &out2, const OT &pool, int64_t adj_layout) {
   TORCH_CHECK(x.dim() == 3 && w.dim() == 2 && w.size(1) == x.size(2), "truss_mi355: gcn_layer_fused: x [B, N, K], w [C, K]");
   const int64_t B = x.size(0), N = x.size(1), K = x.size(2), C = w.size(0);
-  a = layer_args(b, B, N, K, C, act, &x, adj, nbr, w);
+  a = layer_args(b, B, N, K, C, act, &x, adj, nbr, w, adj_layout);
   a.bias = ptr<const float>(b, bias, at::kFloat, "bias", C);
   TORCH_CHECK(!present(out) || (out->dim() == 3 && out->size(0) == B && out->size(1) == N && out->size(2) == C),
               "truss_mi355: gcn_layer_fused: out must be [B, N, C]");
@@ -345,12 +377,12 @@ void fused_args(const Backend &b, truss_gcn_layer_args_t &a, truss_gcn_epilogue_
 }
 void gcn_layer_fused(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
                      const OT &out, int64_t act, const OT &w_split, int64_t kind, const OT &w2, const OT &bias2, const OT &adj2, const OT &nbr2,
-                     int64_t act2, const OT &out2, const OT &pool) {
+                     int64_t act2, const OT &out2, const OT &pool, int64_t adj_layout) {
   const Backend &b = backend(lib);
   need(b.gcn_layer_fused, "truss_gcn_layer_fused");
   truss_gcn_layer_args_t a;
   truss_gcn_epilogue_t e;
-  fused_args(b, a, e, x, adj, nbr, w, bias, out, act, w_split, kind, w2, bias2, adj2, nbr2, act2, out2, pool);
+  fused_args(b, a, e, x, adj, nbr, w, bias, out, act, w_split, kind, w2, bias2, adj2, nbr2, act2, out2, pool, adj_layout);
   check_rc(b, b.gcn_layer_fused(&a, &e, (void *)stream), "truss_gcn_layer_fused");
 }
 
@@ -358,12 +390,12 @@ void gcn_layer_fused(int64_t lib, int64_t stream, const at::Tensor &x, const at:
 // (out required, accumulate allowed), kind 1 / 2: with the epilogue of gcn_layer_fused == truss_gcn_layer_terms
 void gcn_layer_terms(int64_t lib, int64_t stream, const at::Tensor &x, const at::Tensor &adj, const OT &nbr, const at::Tensor &w, const OT &bias,
                      const OT &out, int64_t act, const OT &w_split, int64_t kind, const OT &w2, const OT &bias2, const OT &adj2, const OT &nbr2,
-                     int64_t act2, const OT &out2, const OT &pool, bool accumulate, int64_t terms) {
+                     int64_t act2, const OT &out2, const OT &pool, bool accumulate, int64_t terms, int64_t adj_layout) {
   const Backend &b = backend(lib);
   need(b.gcn_layer_terms, "truss_gcn_layer_terms");
   truss_gcn_layer_args_t a;
   truss_gcn_epilogue_t e;
-  fused_args(b, a, e, x, adj, nbr, w, bias, out, act, w_split, kind, w2, bias2, adj2, nbr2, act2, out2, pool);
+  fused_args(b, a, e, x, adj, nbr, w, bias, out, act, w_split, kind, w2, bias2, adj2, nbr2, act2, out2, pool, adj_layout);
   TORCH_CHECK(kind != 0 || present(out), "truss_mi355: gcn_layer_terms: out must be [B, N, C] for a plain layer (kind 0)");
   a.accumulate = accumulate ? 1 : 0;
   TORCH_CHECK(terms >= INT32_MIN && terms <= INT32_MAX, "truss_mi355: gcn_layer_terms: terms out of range");
@@ -377,7 +409,7 @@ void gcn_layer_group(int64_t lib, int64_t stream, at::TensorList x, at::TensorLi
                      const c10::List<OT> &bias, const c10::List<OT> &out, at::IntArrayRef act, const c10::List<bool> &accumulate,
                      at::TensorList w_split, int64_t steps_per_chain, int64_t kind, const c10::List<OT> &w2, const c10::List<OT> &bias2,
                      const c10::List<OT> &adj2, const c10::List<OT> &nbr2, at::IntArrayRef act2, const c10::List<OT> &out2,
-                     const c10::List<OT> &pool, int64_t terms) {
+                     const c10::List<OT> &pool, int64_t terms, at::IntArrayRef adj_layout) {
   const Backend &b = backend(lib);
   need(b.gcn_layer_group, "truss_gcn_layer_group");
   const size_t L = x.size();
@@ -385,6 +417,7 @@ void gcn_layer_group(int64_t lib, int64_t stream, at::TensorList x, at::TensorLi
   TORCH_CHECK(adj.size() == L && w.size() == L && act.size() == L && accumulate.size() == L && w_split.size() == L && per_layer(nbr) &&
                   per_layer(bias) && out.size() == L,
               "truss_mi355: gcn_layer_group takes one entry per layer in every list");
+  TORCH_CHECK(adj_layout.empty() || adj_layout.size() == L, "truss_mi355: gcn_layer_group: adj_layout is empty (dense) or holds one entry per layer");
   TORCH_CHECK(kind != 0 ? (per_layer(w2) && per_layer(bias2) && per_layer(adj2) && per_layer(nbr2) && act2.size() == L && per_layer(out2) &&
                            per_layer(pool))
                         : (w2.empty() && bias2.empty() && adj2.empty() && nbr2.empty() && act2.empty() && out2.empty() && pool.empty()),
@@ -398,7 +431,7 @@ void gcn_layer_group(int64_t lib, int64_t stream, at::TensorList x, at::TensorLi
   for (size_t i = 0; i < L; ++i) {
     fused_args(b, args[i], epi[i], x[i], adj[i], at_or_none(nbr, i), w[i], at_or_none(bias, i), out.get(i), act[i], OT(w_split[i]), kind,
                at_or_none(w2, i), at_or_none(bias2, i), at_or_none(adj2, i), at_or_none(nbr2, i), kind != 0 ? act2[i] : 0, at_or_none(out2, i),
-               at_or_none(pool, i));
+               at_or_none(pool, i), adj_layout.empty() ? 0 : adj_layout[i]);
     TORCH_CHECK(kind != 0 || present(out.get(i)), "truss_mi355: gcn_layer_group: out must be [B, N, C] for a plain layer (kind 0)");
     args[i].accumulate = accumulate.get(i) ? 1 : 0;
   }
@@ -968,6 +1001,7 @@ extern "C" int truss_torch_bind(int lib, const char *path, const char **missing)
 #define X(field, symbol, required) b.field = (decltype(b.field))find(#symbol, required);
   TRUSS_ENTRY_POINTS(X)
 #undef X
+  b.topo_neighbors = (decltype(b.topo_neighbors))find("truss_topo_neighbors", false);
   auto backend_name = (decltype(&truss_backend))find("truss_backend", true);
   dlclose(h);                    // only the reference taken above: the caller keeps the image loaded
   if (lacks) {
@@ -1000,12 +1034,15 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("obs(int lib, int topo, int stream, int n_envs, int n_nodes, int n_elems, Tensor x, Tensor y, Tensor sec, Tensor max_up, "
         "Tensor max_down, Tensor target, Tensor disp, Tensor q0, Tensor sr, Tensor comp, Tensor env_params, Tensor(a!)? x_n, "
         "Tensor(b!)? A_s, Tensor(c!)? A_n_ts, Tensor(d!)? A_n_cs, Tensor(e!)? nN_x_n, Tensor(f!)? nN_x_e) -> ()");
+  m.def("obs_flags(int lib, int topo, int stream, int flags, int n_envs, int n_nodes, int n_elems, Tensor x, Tensor y, Tensor sec, Tensor max_up, "
+        "Tensor max_down, Tensor target, Tensor disp, Tensor q0, Tensor sr, Tensor comp, Tensor env_params, Tensor(a!)? x_n, "
+        "Tensor(b!)? A_s, Tensor(c!)? A_n_ts, Tensor(d!)? A_n_cs, Tensor(e!)? nN_x_n, Tensor(f!)? nN_x_e) -> ()");   // truss_obs with args->flags
   m.def("front(int lib, int stream, int max_front, int flags, Tensor points, Tensor n_points, Tensor? ref_points, "
         "Tensor(a!)? front_idx, Tensor(b!)? n_front, Tensor(c!)? hv_front, Tensor(d!)? hv_all, Tensor(e!)? metrics) -> ()");
   m.def("gcn_aggregate(int lib, int stream, Tensor adj, Tensor h, Tensor? bias, Tensor(a!) out, int act) -> ()");
   m.def("gcn_aggregate_sparse(int lib, int stream, Tensor adj, Tensor nbr, Tensor h, Tensor? bias, Tensor(a!) out, int act) -> ()");
   m.def("gcn_layer(int lib, int stream, Tensor x, Tensor adj, Tensor? nbr, Tensor w, Tensor? bias, Tensor(a!) out, int act, bool accumulate, "
-        "Tensor? w_split) -> ()");
+        "Tensor? w_split, int adj_layout=0) -> ()");
   m.def("gcn_split_w(int lib, int stream, Tensor w, Tensor(a!) out) -> ()");
   m.def("gcn_level(int lib, int stream, Tensor[] x, Tensor[] adj, Tensor?[] nbr, Tensor[] w, Tensor[] bias, Tensor(a!)[] out, Tensor(b!)[] x_agg, "
         "int[] act) -> ()");
@@ -1020,13 +1057,13 @@ TORCH_LIBRARY(truss_mi355, m) {
         "Tensor cand_points, Tensor cand_y, Tensor cand_sec, Tensor(a!) pts_out, Tensor(b!) y_out, Tensor(c!) sec_out, Tensor(d!) n_out, "
         "Tensor(e!)? accepted, Tensor(f!)? front_idx, Tensor(g!)? hv_front, Tensor(h!)? metrics) -> ()");
   m.def("gcn_layer_fused(int lib, int stream, Tensor x, Tensor adj, Tensor? nbr, Tensor w, Tensor? bias, Tensor(a!)? out, int act, Tensor? w_split, "
-        "int kind, Tensor? w2, Tensor? bias2, Tensor? adj2, Tensor? nbr2, int act2, Tensor(b!)? out2, Tensor(c!)? pool) -> ()");
+        "int kind, Tensor? w2, Tensor? bias2, Tensor? adj2, Tensor? nbr2, int act2, Tensor(b!)? out2, Tensor(c!)? pool, int adj_layout=0) -> ()");
   m.def("gcn_layer_terms(int lib, int stream, Tensor x, Tensor adj, Tensor? nbr, Tensor w, Tensor? bias, Tensor(a!)? out, int act, Tensor? w_split, "
         "int kind, Tensor? w2, Tensor? bias2, Tensor? adj2, Tensor? nbr2, int act2, Tensor(b!)? out2, Tensor(c!)? pool, bool accumulate, "
-        "int terms) -> ()");
+        "int terms, int adj_layout=0) -> ()");
   m.def("gcn_layer_group(int lib, int stream, Tensor[] x, Tensor[] adj, Tensor?[] nbr, Tensor[] w, Tensor?[] bias, Tensor(a!)?[] out, int[] act, "
         "bool[] accumulate, Tensor[] w_split, int steps_per_chain, int kind, Tensor?[] w2, Tensor?[] bias2, Tensor?[] adj2, Tensor?[] nbr2, "
-        "int[] act2, Tensor(b!)?[] out2, Tensor(c!)?[] pool, int terms) -> ()");
+        "int[] act2, Tensor(b!)?[] out2, Tensor(c!)?[] pool, int terms, int[] adj_layout=[]) -> ()");
   m.def("pair_setup(int lib, int stream, int rep, int seed, int game_step, float[] dtab, Tensor idx, Tensor ms, Tensor pts, Tensor n, Tensor arch_y, "
         "Tensor arch_sec, Tensor c_x, Tensor c_target, Tensor c_params, Tensor ref_points, Tensor? env_ids, Tensor? frac_tab, Tensor(a!) par_x, Tensor(b!) par_target, "
         "Tensor(c!) par_params, Tensor(d!) par_y, Tensor(e!) par_sec, Tensor(f!) cand_x, Tensor(g!) cand_target, Tensor(h!) cand_params, "
@@ -1045,6 +1082,7 @@ static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);
   TRUSS_OPERATOR_ENTRIES(X)
 #undef X
+  m.impl("obs_flags", obs_flags);   // a second operator of truss_obs: no table line of its own
 }
 TORCH_LIBRARY_IMPL(truss_mi355, CPU, m) { register_operators(m); }    // the emulator library of the test-suite binds here
 TORCH_LIBRARY_IMPL(truss_mi355, CUDA, m) { register_operators(m); }   // = HIP on ROCm: the product library
@@ -1052,4 +1090,5 @@ TORCH_LIBRARY_IMPL(truss_mi355, Meta, m) {                            // tracing
 #define X(field, symbol, required) m.impl(#field, torch::CppFunction::makeFromBoxedFunction<&noop_boxed>());
   TRUSS_OPERATOR_ENTRIES(X)
 #undef X
+  m.impl("obs_flags", torch::CppFunction::makeFromBoxedFunction<&noop_boxed>());
 }

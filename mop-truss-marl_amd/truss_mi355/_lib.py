@@ -18,6 +18,7 @@ TRUSS_ABI_VERSION = 3
 F_NO_DECODE = 0x1
 F_CLAMP_INPLACE = 0x2
 F_EMIT_OBS = 0x4
+F_OBS_COMPACT = 0x8       # with F_EMIT_OBS (and as ObsArgs.flags): A_s / A_n_ts / A_n_cs as [B, N, Kc] rows through the neighbour table
 STATUS_NOT_SPD = 1        # status[] bits (include/truss_mi355.h)
 STATUS_OBS_TIMEOUT = 2
 NPARAM = 8
@@ -179,6 +180,7 @@ _LATER_ENTRIES = [
     ("truss_gcn_level_aggregate", [_vp, _i32, _vp]),
     ("truss_optim_step", [C.POINTER(OptimArgs), _vp]),
     ("truss_topo_lds_info", [_vp, _i32, _vp, _vp, _i32, _vp, _i32]),
+    ("truss_topo_neighbors", [_vp, _vp, _i32, C.POINTER(_i32)]),
     ("truss_critic_tail", [C.POINTER(CriticTailArgs), _i32, _vp]),
     ("truss_critic_tail_backward", [C.POINTER(CriticTailBwd), _i32, _vp]),
 ]
@@ -221,6 +223,7 @@ class TrussLib:
         self.has_level_aggregate = "truss_gcn_level_aggregate" in found                      # a level's neighbour sums through the node table
         self.has_optim_step = "truss_optim_step" in found                                    # clip and Adam of the update as one call
         self.has_critic_tail = {"truss_critic_tail", "truss_critic_tail_backward"} <= found  # pools and dense layers of a critic pass
+        self.has_obs_compact = "truss_topo_neighbors" in found                               # the compact observation layout (F_OBS_COMPACT)
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")
         self.backend = d.truss_backend().decode()

@@ -94,21 +94,46 @@ class BatchedTruss:
 
     OBS_KEYS = ("x_n", "A_s", "A_n_ts", "A_n_cs", "nN_x_n", "nN_x_e")
 
-    def obs_buffers(self):
-        """The env's own observation tensors (allocated on first use)."""
-        if not hasattr(self, "_obs"):
+    OBS_LAYOUTS = ("dense", "compact")
+
+    def obs_width(self, layout="dense"):
+        """Columns of A_s / A_n_ts / A_n_cs in `layout`: N (dense), or Kc, the width of the neighbour table (compact).  The compact
+        layout is trusted only after the library's own table (truss_topo_neighbors) has been held against
+        TrussTopology.neighbor_table(): the two sides index the same [N, Kc] rows or the layout is refused."""
+        if layout not in self.OBS_LAYOUTS:
+            raise ValueError(f"obs layout must be one of {self.OBS_LAYOUTS}, got {layout!r}")
+        if layout == "dense":
+            return self.N
+        if not hasattr(self, "_kc"):
+            if not self.lib.has_obs_compact:
+                raise _lib.TrussError("the bound native library has no truss_topo_neighbors: no compact observation layout")
+            with self._on_device():
+                mine, its = self.topo.neighbor_table(), self.topo.native_neighbors(self.lib)
+            if mine.shape != its.shape or not np.array_equal(mine, its):
+                raise _lib.TrussError("the library's neighbour table differs from TrussTopology.neighbor_table(): "
+                                      "the compact observation layout cannot be trusted")
+            self._kc = int(mine.shape[1])
+        return self._kc
+
+    def obs_buffers(self, layout="dense"):
+        """The env's own observation tensors in `layout` (allocated on first use; one set per layout)."""
+        W = self.obs_width(layout)
+        if not hasattr(self, "_obs_by_layout"):
+            self._obs_by_layout = {}
+        if layout not in self._obs_by_layout:
             B, N, E = self.B, self.N, self.E
             mk = lambda *sh: torch.empty(sh, dtype=torch.float32, device=self.device)
-            self._obs = dict(x_n=mk(B, N, 13), A_s=mk(B, N, N), A_n_ts=mk(B, N, N), A_n_cs=mk(B, N, N),
-                             nN_x_n=mk(B, N, 12), nN_x_e=mk(B, E, 21))
-        return self._obs
+            self._obs_by_layout[layout] = dict(x_n=mk(B, N, 13), A_s=mk(B, N, W), A_n_ts=mk(B, N, W), A_n_cs=mk(B, N, W),
+                                               nN_x_n=mk(B, N, 12), nN_x_e=mk(B, E, 21))
+        return self._obs_by_layout[layout]
 
-    def _obs_out(self, out, nact):
+    def _obs_out(self, out, nact, layout="dense"):
         """Validated observation outputs: None -> the env's own buffers; a dict may leave tensors out."""
+        W = self.obs_width(layout)
         if out is None or out is True:
-            return self.obs_buffers()
+            return self.obs_buffers(layout)
         N, E = self.N, self.E
-        shapes = dict(x_n=(N, 13), A_s=(N, N), A_n_ts=(N, N), A_n_cs=(N, N), nN_x_n=(N, 12), nN_x_e=(E, 21))
+        shapes = dict(x_n=(N, 13), A_s=(N, W), A_n_ts=(N, W), A_n_cs=(N, W), nN_x_n=(N, 12), nN_x_e=(E, 21))
         for k in self.OBS_KEYS:
             t = out.get(k)
             if t is None:
@@ -137,10 +162,10 @@ class BatchedTruss:
                 o.get("x_n"), o.get("A_s"), o.get("A_n_ts"), o.get("A_n_cs"), o.get("nN_x_n"), o.get("nN_x_e"))
 
     def _step_op(self, flags, n_envs, a_geo, a_topo, coin, mu_in, md_in, y_in, sec_in, y_out, sec_out, want_energy=True,
-                 obs=None):
-        """torch.ops.truss_mi355.step: one truss_step launch (+ the observation tensors with `obs`)."""
+                 obs=None, obs_layout="dense"):
+        """torch.ops.truss_mi355.step: one truss_step launch (+ the observation tensors with `obs`, in `obs_layout`)."""
         if obs is not None:
-            flags |= _lib.F_EMIT_OBS
+            flags |= _lib.F_EMIT_OBS | (_lib.F_OBS_COMPACT if obs_layout == "compact" else 0)
         with self._on_device():
             ops.call(self._ops.step, self._lib_id, self.h.value, ops.stream_of(self.device), flags, n_envs, self.N, self.E,
                            *self._step_tensors(a_geo, a_topo, coin, mu_in, md_in, y_in, sec_in, y_out, sec_out, want_energy, obs))
@@ -180,17 +205,19 @@ class BatchedTruss:
             raise ValueError(f"n_active {n} outside 0..{self.B}")
         return n
 
-    def analyze(self, set_normalisers: bool = False, n_active=None, obs=None):
+    def analyze(self, set_normalisers: bool = False, n_active=None, obs=None, obs_layout="dense"):
         """Model.restore(); Model.gen_all() on the current design (reset path).  With
         set_normalisers the raw objectives become int_obj1/int_obj2 (Game_research04.__init__,
         truss2D_ENV.py:264-274).  n_active: only the first n envs of the resident buffers (callers that
         compact their live envs to the front, truss_mi355/marl.py).  obs: True / dict -> also write the
-        observation tensors (`_game_get_1_state`, truss2D_ENV.py:336-351) in the same native call."""
+        observation tensors (`_game_get_1_state`, truss2D_ENV.py:336-351) in the same native call.  obs_layout: "dense" |
+        "compact" -- A_s / A_n_ts / A_n_cs as [., N, N], or as [., N, Kc] rows through TrussTopology.neighbor_table()."""
         n = self._n(n_active)
         if n == 0:
             return None
-        out = None if obs is None or obs is False else self._obs_out(obs, n)
-        self._step_op(_lib.F_NO_DECODE, n, None, None, None, None, None, self.y, self.sec, self.y, self.sec, obs=out)
+        out = None if obs is None or obs is False else self._obs_out(obs, n, obs_layout)
+        self._step_op(_lib.F_NO_DECODE, n, None, None, None, None, None, self.y, self.sec, self.y, self.sec, obs=out,
+                      obs_layout=obs_layout)
         if set_normalisers:
             self.env_params[:, _lib.P_INTOBJ1] = self.obj[:, 0].double()
             self.env_params[:, _lib.P_INTOBJ2] = self.obj[:, 1].double()
@@ -200,16 +227,16 @@ class BatchedTruss:
 
     # ---- the transition ---------------------------------------------------------------------
     def step(self, a_geo, a_topo, coin=None, max_up_in=None, max_down_in=None, clamp_inplace=False, n_active=None,
-             obs=None):
+             obs=None, obs_layout="dense"):
         """One `_game_modify` per env from the current design; the new design becomes current.
         a_geo [B,N,2], a_topo [B,N,3] float32 on the env's device ([n_active, ...] with n_active).
         obs: True (the env's own buffers) or a dict of output tensors -> the observation tensors of the new
         design (state_data + state_data_not_norm, truss2D_ENV.py:497-500) are written by the same native call
-        -- by the same kernel launch where `fused_obs` -- and returned."""
+        -- by the same kernel launch where `fused_obs` -- and returned.  obs_layout: as in analyze()."""
         B, N = self._n(n_active), self.N
         if B == 0:
             return None
-        out = None if obs is None or obs is False else self._obs_out(obs, B)
+        out = None if obs is None or obs is False else self._obs_out(obs, B, obs_layout)
         if coin is None:
             coin = self._coin0
         nxt = self.cur ^ 1
@@ -223,7 +250,7 @@ class BatchedTruss:
             raise ValueError(f"coin: expected [{B}], got {tuple(coin.shape)}")
         # dtype / device / contiguity / size of every tensor are checked by the operator itself
         self._step_op(flags, B, a_geo, a_topo, coin, max_up_in, max_down_in, self.ybuf[self.cur], self.secbuf[self.cur],
-                      self.ybuf[nxt], self.secbuf[nxt], obs=out)
+                      self.ybuf[nxt], self.secbuf[nxt], obs=out, obs_layout=obs_layout)
         self.cur = nxt
         return out
 
@@ -243,17 +270,18 @@ class BatchedTruss:
         if n_steps & 1:
             self.cur = nxt
 
-    def observe(self, out=None, n_active=None):
+    def observe(self, out=None, n_active=None, obs_layout="dense"):
         """state_data + state_data_not_norm (truss2D_ENV.py:40-193) for the current design and the last
         analysis, for every env: x_n[B,N,13], A_s/A_n_ts/A_n_cs[B,N,N], nN_x_n[B,N,12], nN_x_e[B,E,21]
         (device tensors).  A_n, mask and nC_e are topology-static: TrussTopology.normalized_adjacency()
-        / .incidence()."""
+        / .incidence().  obs_layout "compact": the three matrices as [B,N,Kc] rows through TrussTopology.neighbor_table()."""
         nact = self._n(n_active)
-        out = self._obs_out(out, nact)
+        out = self._obs_out(out, nact, obs_layout)
         if nact == 0:
             return out
         with self._on_device():
-            ops.call(self._ops.obs, self._lib_id, self.h.value, ops.stream_of(self.device), nact, self.N, self.E, self.x, self.y, self.sec,
+            op = (self._ops.obs,) if obs_layout == "dense" else (self._ops.obs_flags, _lib.F_OBS_COMPACT)   # dense: the call it always was
+            ops.call(op[0], self._lib_id, self.h.value, ops.stream_of(self.device), *op[1:], nact, self.N, self.E, self.x, self.y, self.sec,
                           self.max_up, self.max_down, self.target, self.disp, self.q0, self.sr, self.comp, self.env_params,
                           out.get("x_n"), out.get("A_s"), out.get("A_n_ts"), out.get("A_n_cs"), out.get("nN_x_n"), out.get("nN_x_e"))
         return out

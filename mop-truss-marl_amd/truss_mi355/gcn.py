@@ -21,6 +21,22 @@ def _adj(a, expanded=False):
     return None if a is None else a.contiguous()
 
 
+COMPACT_ADJ = ("A_s", "A_ts", "A_cs")                      # the actor inputs the compact observation layout covers (A_n, A_p stay dense)
+
+
+def expand_compact(adj, nbr):
+    """compact rows [.., N, Kc] of the table nbr [N, Kc] (the compact observation layout, TRUSS_F_OBS_COMPACT) -> the dense [.., N, N]
+    matrix: zeros, and every slot's value at its column.  The unused slots hold +0 and add it to column 0."""
+    N, idx = adj.shape[-2], nbr.clamp(min=0).long()
+    dense = adj.new_zeros(adj.shape[:-1] + (N,))
+    return dense.scatter_add_(-1, idx.expand_as(adj), adj * (nbr >= 0))
+
+
+def _native_compact(lib):
+    """the layer kernels of `lib` read compact adjacencies themselves (adj_layout 1); elsewhere they are expanded on the host"""
+    return lib.backend == "hip" and lib.has_obs_compact
+
+
 def gcn_aggregate(lib, adj, h, bias, act, nbr=None):
     """act(adj @ h + bias) through the fused HIP kernels `truss_gcn_aggregate` / `truss_gcn_aggregate_sparse` (inference only, float32).
     adj [N,N] (shared) or [B,N,N]; h [B,N,C] contiguous; act in {None,'relu','sigmoid'}.
@@ -116,23 +132,34 @@ def _split_image(lib, x, w, nbr, precision, w_split):
     return w_split if w_split is not None else split_weights(lib, w)
 
 
+def _layout(lib, adj, nbr, compact):
+    """(adj, adj_layout) as the operators take a layer's adjacency: a compact one as it is where the kernels read it, else expanded"""
+    if not compact:
+        return adj, 0
+    if nbr is None:
+        raise ValueError("a compact adjacency needs its neighbour table (nbr)")
+    return (adj, 1) if _native_compact(lib) else (expand_compact(adj, nbr), 0)
+
+
 def _launch_layer(lib, x, adj, w, bias, act, nbr, precision, w_split, out, accumulate=False, kind=0, w2=None, bias2=None, adj2=None,
-                  nbr2=None, act2=None, out2=None, pool=None):
+                  nbr2=None, act2=None, out2=None, pool=None, compact=False):
     """one layer launch: `truss_gcn_layer` (kind 0) or `truss_gcn_layer_fused` (kind 1: head epilogue, 2: pool epilogue) under
-    "bf16x3" / "f32"; `truss_gcn_layer_terms`, which takes both, under "bf16x2" / "bf16" inside the split-weight envelope"""
+    "bf16x3" / "f32"; `truss_gcn_layer_terms`, which takes both, under "bf16x2" / "bf16" inside the split-weight envelope.
+    compact: adj holds the [.., N, Kn] rows of `nbr` (adj_layout 1 of the C ABI); adj2 is always dense"""
     _check_precision(precision)
     ws = _split_image(lib, x, w, nbr, precision, w_split)
+    adj, layout = _layout(lib, adj, nbr, compact)
     ns, layer = ops.namespace(), (ops.bind(lib), ops.stream_of(x.device), x, _adj(adj), nbr, w, bias, out, _ACT_CODE[act])
     epilogue = (kind, w2, bias2, _adj(adj2), nbr2, _ACT_CODE[act2], out2, pool)
     if ws is not None and precision != "bf16x3":
-        ops.call(ns.gcn_layer_terms, *layer, ws, *epilogue, bool(accumulate), _BF16_TERMS[precision])
+        ops.call(ns.gcn_layer_terms, *layer, ws, *epilogue, bool(accumulate), _BF16_TERMS[precision], layout)
     elif kind:
-        ops.call(ns.gcn_layer_fused, *layer, ws, *epilogue)
+        ops.call(ns.gcn_layer_fused, *layer, ws, *epilogue, layout)
     else:
-        ops.call(ns.gcn_layer, *layer, bool(accumulate), ws)
+        ops.call(ns.gcn_layer, *layer, bool(accumulate), ws, layout)
 
 
-def gcn_layer(lib, x, adj, w, bias, act, nbr=None, out=None, accumulate=False, precision="bf16x3", w_split=None):
+def gcn_layer(lib, x, adj, w, bias, act, nbr=None, out=None, accumulate=False, precision="bf16x3", w_split=None, compact=False):
     """One whole GCN layer through the hand-written MFMA kernel (`truss_gcn_layer`, csrc/truss_gcn.h):
     out = act(adj @ (x @ w.T) + bias), or out += ... with `accumulate`; float32 in and out, inference (no autograd).
     x [B,N,K] contiguous; adj [N,N] (shared) or [B,N,N]; w [C,K] = nn.Linear.weight, C <= 224; nbr: int16 [N,Kn] sparsity pattern of
@@ -143,28 +170,33 @@ def gcn_layer(lib, x, adj, w, bias, act, nbr=None, out=None, accumulate=False, p
     the first term of both operands (`truss_gcn_layer_terms`; three products / one product): reduced precision for inference,
     |out - ref64| <= (2^-13 + 1e-6) Mag / (2^-6 + 1e-6) Mag with Mag = |A| (|X| |W|^T) + |b| (+ |out0|), operands truncated (every
     product biased towards zero); a layer outside that envelope runs in float32 as under every precision.
-    w_split: split_weights(lib, w) if the caller keeps it (one image serves all precisions)."""
+    w_split: split_weights(lib, w) if the caller keeps it (one image serves all precisions).
+    compact: adj is [N,Kn] / [B,N,Kn], the rows of the compact observation layout through `nbr` (required then): term t of row i is
+    adj[i, t], its source row nbr[i, t] -- the same coefficients in the same order, so the result is bit for bit that of the dense
+    call.  A library whose kernels do not read that layout gets the adjacency expanded to dense first (`expand_compact`)."""
     if out is None:
         assert not accumulate
         out = torch.empty((x.shape[0], x.shape[1], w.shape[0]), dtype=torch.float32, device=x.device)
-    _launch_layer(lib, x, adj, w, bias, act, nbr, precision, w_split, out, accumulate)
+    _launch_layer(lib, x, adj, w, bias, act, nbr, precision, w_split, out, accumulate, compact=compact)
     return out
 
 
 def _gcn_layer_fused(lib, x, adj, w, bias, act, nbr, precision, w_split, out, kind, w2=None, bias2=None, adj2=None, nbr2=None, act2=None,
-                     out2=None, pool=None):
+                     out2=None, pool=None, compact=False):
     """`truss_gcn_layer_fused`: the layer of `gcn_layer` with a consumer of its output in the epilogue of the same launch
     (precision "bf16x2" / "bf16", inside the split-weight envelope: `truss_gcn_layer_terms` with the same epilogue)"""
-    _launch_layer(lib, x, adj, w, bias, act, nbr, precision, w_split, out, False, kind, w2, bias2, adj2, nbr2, act2, out2, pool)
+    _launch_layer(lib, x, adj, w, bias, act, nbr, precision, w_split, out, False, kind, w2, bias2, adj2, nbr2, act2, out2, pool, compact)
 
 
-def gcn_layer_head(lib, x, adj, w, bias, act, w2, bias2, adj2, act2, nbr=None, nbr2=None, precision="bf16x3", w_split=None, out=None):
+def gcn_layer_head(lib, x, adj, w, bias, act, w2, bias2, adj2, act2, nbr=None, nbr2=None, precision="bf16x3", w_split=None, out=None,
+                   compact=False):
     """A hidden GCN layer and the narrow layer that consumes it in ONE launch (`truss_gcn_layer_fused`, head epilogue):
     act2(adj2 @ (V @ w2.T) + bias2) [B, N, c2] with V = act(adj @ (x @ w.T) + bias) as `gcn_layer` computes it -- V goes from the
     accumulators through LDS into the head and is written to HBM only if `out` [B, N, C] is given.  w2 [c2 <= 8, C] =
-    nn.Linear.weight of the head; adj2 / nbr2: the head's own adjacency and pattern (as adj / nbr); the rest as for `gcn_layer`."""
+    nn.Linear.weight of the head; adj2 / nbr2: the head's own adjacency and pattern (as adj / nbr); the rest as for `gcn_layer`
+    (compact: the layout of adj only -- adj2 is dense)."""
     out2 = torch.empty((x.shape[0], x.shape[1], w2.shape[0]), dtype=torch.float32, device=x.device)
-    _gcn_layer_fused(lib, x, adj, w, bias, act, nbr, precision, w_split, out, 1, w2, bias2, adj2, nbr2, act2, out2=out2)
+    _gcn_layer_fused(lib, x, adj, w, bias, act, nbr, precision, w_split, out, 1, w2, bias2, adj2, nbr2, act2, out2=out2, compact=compact)
     return out2
 
 
@@ -184,7 +216,8 @@ def gcn_layer_group(lib, chains, precision="bf16x3", epilogues=None):
     """Several split-weight GCN layers in ONE launch (`truss_gcn_layer_group`, csrc/truss_gcn_group.h): the same bits as running them
     one by one through `gcn_layer` / `gcn_layer_head` / `gcn_layer_pool` in chain order.
     chains: a list of chains of equal length; a chain is a list of steps that write the same `out`, a step a dict with the arguments of
-    `gcn_layer` by name: x, adj, w, bias, act, out, w_split (required: `split_weights(lib, w)`), and optionally nbr, accumulate.
+    `gcn_layer` by name: x, adj, w, bias, act, out, w_split (required: `split_weights(lib, w)`), and optionally nbr, accumulate,
+    compact (the step's adj holds the compact rows of its nbr).
     Chains must not depend on each other; a step must not read the chain's `out`.  All layers share B, N and table-or-dense.
     epilogues: None, or one dict per chain (chains of one step; out may then be None): kind "head" with w2, bias2, adj2, act2, out2
     and optionally nbr2, or kind "pool" with pool -- all of one kind.
@@ -206,9 +239,10 @@ def gcn_layer_group(lib, chains, precision="bf16x3", epilogues=None):
         epi = [ecol("w2"), ecol("bias2"), [_adj(a) for a in ecol("adj2")], ecol("nbr2"), [_ACT_CODE[e.get("act2")] for e in epilogues],
                ecol("out2"), ecol("pool")]
     device = steps[0]["x"].device if steps else torch.device("cpu")
-    ops.call(ops.namespace().gcn_layer_group, ops.bind(lib), ops.stream_of(device), col("x"), [_adj(a) for a in col("adj")], col("nbr"),
+    laid = [_layout(lib, s["adj"], s.get("nbr"), s.get("compact", False)) for s in steps]
+    ops.call(ops.namespace().gcn_layer_group, ops.bind(lib), ops.stream_of(device), col("x"), [_adj(a) for a, _ in laid], col("nbr"),
              col("w"), col("bias"), col("out"), [_ACT_CODE[s["act"]] for s in steps], [bool(s.get("accumulate", False)) for s in steps],
-             col("w_split"), per_chain, kind, *epi, _BF16_TERMS[precision])
+             col("w_split"), per_chain, kind, *epi, _BF16_TERMS[precision], [l for _, l in laid] if any(l for _, l in laid) else [])
 
 
 def level_forward(lib):
@@ -351,11 +385,12 @@ def _materialise(actor, t):
                            + tuple((head, layer, adj2) for layer, head, _, adj2 in _ACTOR_HEADS)):
         layer, a = getattr(actor, name), t[adj]
         if isinstance(layer.lin.weight, torch.nn.parameter.UninitializedParameter):
+            n = a.shape[-2]                                  # (a compact adjacency [.., N, Kc] stands in as an empty [1, N, N])
             with torch.no_grad():
-                layer(a.new_zeros((1, a.shape[-1], width(src))), a[:1] if a.dim() == 3 else a)
+                layer(a.new_zeros((1, n, width(src))), (a[:1] if a.dim() == 3 else a) if a.shape[-1] == n else a.new_zeros((1, n, n)))
 
 
-def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False, precision="bf16x3"):
+def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False, precision="bf16x3", compact=False):
     """truss2D_RL.multimodes_actor.forward (truss2D_RL.py:49-120) for inference, every GCN layer ONE launch of the fused MFMA
     kernel (`gcn_layer`: neighbourhood sum on the input rows, product with W^T on the matrix cores, bias + activation in the
     epilogue; H = X W never exists in HBM); the five second-level layers accumulate their sum x3 in place.  Same values as the
@@ -369,11 +404,14 @@ def actor_infer(lib, actor, ins, nbr=None, nbr_p=None, fused=False, precision="b
     summation order; a layer outside the kernel's envelope takes the unfused path.
     precision: handed to every layer (`gcn_layer`): "bf16x3" (default, float32 accuracy), "f32", or the reduced "bf16x2" / "bf16"
     for the hidden layers -- the action heads and every other layer outside the split-weight envelope stay float32.  The cached
-    split weights (`layer_split_weights`) are the same for all of them."""
-    return _actors_forward(lib, [actor], ins, nbr, nbr_p, fused, precision, group=False)[0]
+    split weights (`layer_split_weights`) are the same for all of them.
+    compact: A_s, A_ts and A_cs of `ins` are [B, N, Kc] rows of the compact observation layout through `nbr` (A_n and A_p stay
+    dense): the layers over them read the rows as they are (`gcn_layer(compact=True)`), bit for bit the dense result; a layer outside
+    `gcn_layer_supported` gets the dense matrix back first (`expand_compact`) and takes the fallback it always took."""
+    return _actors_forward(lib, [actor], ins, nbr, nbr_p, fused, precision, group=False, compact=compact)[0]
 
 
-def actors_infer(lib, actors, ins, nbr=None, nbr_p=None, precision="bf16x3"):
+def actors_infer(lib, actors, ins, nbr=None, nbr_p=None, precision="bf16x3", compact=False):
     """`actor_infer(fused=True)` for EVERY actor of `actors` on the same inputs, level by level: [(geo_a, topo_a) for a in actors],
     bit for bit what the per-actor calls return.  The actors read the same observation tensors and their layers have the same
     shapes; within an actor the layers of one depth do not depend on each other.  So each depth is one launch of
@@ -384,11 +422,11 @@ def actors_infer(lib, actors, ins, nbr=None, nbr_p=None, precision="bf16x3"):
     A level with a layer outside the split-weight envelope (precision "f32", a node graph without a table or with more than nine
     terms per row, a head wider than 8, a library without the entry) runs through the per-layer calls of `actor_infer`; only
     that level does.  Lazy layers are materialised actor by actor in the order of the unfused path; the cached weight images are
-    those of `layer_split_weights`."""
-    return _actors_forward(lib, actors, ins, nbr, nbr_p, True, precision, group=True)
+    those of `layer_split_weights`.  compact: as for `actor_infer`."""
+    return _actors_forward(lib, actors, ins, nbr, nbr_p, True, precision, group=True, compact=compact)
 
 
-def _actors_forward(lib, actors, ins, nbr, nbr_p, fused, precision, group):
+def _actors_forward(lib, actors, ins, nbr, nbr_p, fused, precision, group, compact=False):
     """the walk of `actor_infer` / `actors_infer` over `_ACTOR_*`, depth by depth: with `group`, a depth whose layers are all inside
     the envelope of `gcn_layer_group` is one launch of it for all actors; otherwise the depth runs layer by layer"""
     _check_precision(precision)
@@ -405,13 +443,26 @@ def _actors_forward(lib, actors, ins, nbr, nbr_p, fused, precision, group):
     t["x_n"], t["x_p"] = t["x_n"].contiguous(), t["x_p"].contiguous()
     pat = lambda adj: nbr_p if adj == "A_p" else nbr
     group = group and lib.has_gcn_group and precision != "f32"
+    if compact and nbr is None:
+        raise ValueError("compact adjacencies need the neighbour table (nbr)")
+    cmp = lambda adj: bool(compact) and adj in COMPACT_ADJ       # this input holds compact rows
+    layout = lambda adj: {"compact": True} if cmp(adj) else {}   # (a dense layer is called as it always was)
+    dense = {}                                                   # ... and its dense form, where a fallback needs it (once per input)
+
+    def as_dense(adj):
+        if not cmp(adj):
+            return t[adj]
+        if adj not in dense:
+            dense[adj] = expand_compact(t[adj], nbr)
+        return dense[adj]
 
     def g(layer, x, adj, act="relu", out=None, accumulate=False):
         w, x = layer.lin.weight, x.contiguous()
         if gcn_layer_supported(x.shape[1], w.shape[0], pat(adj)):
             wd, ws = layer_split_weights(lib, layer, x.shape[2])     # (x_n arrives zero-padded to 16 features)
-            return gcn_layer(lib, x, t[adj], wd, layer.bias.detach(), act, pat(adj), out, accumulate, precision=precision, w_split=ws)
-        h = gcn_aggregate(lib, t[adj], torch.nn.functional.linear(x, w).contiguous(), layer.bias, act, pat(adj))
+            return gcn_layer(lib, x, t[adj], wd, layer.bias.detach(), act, pat(adj), out, accumulate, precision=precision, w_split=ws,
+                             **layout(adj))
+        h = gcn_aggregate(lib, as_dense(adj), torch.nn.functional.linear(x, w).contiguous(), layer.bias, act, pat(adj))
         if out is None:
             return h
         return out.add_(h) if accumulate else out.copy_(h)
@@ -420,7 +471,7 @@ def _actors_forward(lib, actors, ins, nbr, nbr_p, fused, precision, group):
         if not (fused and gcn_layer_supported(x.shape[1], layer.lin.weight.shape[0], pat(adj))):
             return g(layer, x, adj).sum(dim=1)
         wd, ws = layer_split_weights(lib, layer, x.shape[2])
-        return gcn_layer_pool(lib, x, t[adj], wd, layer.bias.detach(), "relu", pat(adj), precision=precision, w_split=ws)
+        return gcn_layer_pool(lib, x, as_dense(adj), wd, layer.bias.detach(), "relu", pat(adj), precision=precision, w_split=ws)
 
     def g_head(layer, head, x, adj, adj2):                  # g(head, g(layer, x, adj), adj2, "sigmoid") without the hidden tensor
         w2 = head.lin.weight
@@ -428,8 +479,8 @@ def _actors_forward(lib, actors, ins, nbr, nbr_p, fused, precision, group):
                 and gcn_layer_supported(x.shape[1], w2.shape[0], pat(adj2))):
             return g(head, g(layer, x, adj), adj2, "sigmoid")
         wd, ws = layer_split_weights(lib, layer, x.shape[2])
-        return gcn_layer_head(lib, x, t[adj], wd, layer.bias.detach(), "relu", w2.detach(), head.bias.detach(), t[adj2], "sigmoid",
-                              pat(adj), pat(adj2), precision=precision, w_split=ws)
+        return gcn_layer_head(lib, x, t[adj], wd, layer.bias.detach(), "relu", w2.detach(), head.bias.detach(), as_dense(adj2), "sigmoid",
+                              pat(adj), pat(adj2), precision=precision, w_split=ws, **layout(adj))
 
     def step(layer, x, adj, out=None, accumulate=False):
         """the layer as a step of `gcn_layer_group`, or None outside the envelope of the grouped launch"""
@@ -438,7 +489,8 @@ def _actors_forward(lib, actors, ins, nbr, nbr_p, fused, precision, group):
         wd, ws = layer_split_weights(lib, layer, x.shape[2])
         if ws is None or not _bf16_envelope(x, wd, pat(adj)):
             return None
-        return dict(x=x, adj=t[adj], nbr=pat(adj), w=wd, bias=layer.bias.detach(), act="relu", out=out, accumulate=accumulate, w_split=ws)
+        return dict(x=x, adj=t[adj], nbr=pat(adj), w=wd, bias=layer.bias.detach(), act="relu", out=out, accumulate=accumulate, w_split=ws,
+                    compact=cmp(adj))
 
     def grouped(steps):                                     # the steps if all are inside the envelope and of one width, else None
         ok = group and all(s is not None for s in steps) and len({s["w"].shape[0] for s in steps}) == 1
@@ -494,7 +546,7 @@ def _actors_forward(lib, actors, ins, nbr, nbr_p, fused, precision, group):
     steps = [step(layer, x, adj) for layer, _, adj, _, x in pairs] if group else [None]
     if all(s is not None for s in steps) and all(head.lin.weight.shape[0] <= 8 and gcn_layer_supported(N, head.lin.weight.shape[0], pat(adj2))
                                                   for _, head, _, adj2, _ in pairs):
-        epis = [dict(kind="head", w2=head.lin.weight.detach(), bias2=head.bias.detach(), adj2=t[adj2], nbr2=pat(adj2), act2="sigmoid",
+        epis = [dict(kind="head", w2=head.lin.weight.detach(), bias2=head.bias.detach(), adj2=as_dense(adj2), nbr2=pat(adj2), act2="sigmoid",
                      out2=torch.empty((B, N, head.lin.weight.shape[0]), dtype=torch.float32, device=dev)) for _, head, _, adj2, _ in pairs]
         launch([[s] for s in steps], epis, GROUP_MAX_EPI)
         heads = [e["out2"] for e in epis]

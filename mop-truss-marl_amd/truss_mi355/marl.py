@@ -138,6 +138,11 @@ class BatchedMARL:
     entry); None: "hip" if the environment has TRUSS_REWARD=hip, else "torch".
     replay_storage: "dense" (the default) or "compact" (`DeviceReplay`: adjacencies stored through the neighbour tables, one
     launch per append / sample on the GPU); None: "compact" if the environment has TRUSS_REPLAY_STORAGE=compact, else "dense".
+    obs_layout: how the step / observation kernels hand over the node-graph adjacencies A_s, A_n_ts, A_n_cs of a game step -- "dense"
+    ([., N, N], the default) or "compact" ([., N, Kc] rows through `topo.neighbor_table()`, TRUSS_F_OBS_COMPACT: the actors' layer
+    kernels read the rows as they are, the replay takes them as plain fields; needs a library with `truss_topo_neighbors`, and in the
+    train game replay_storage="compact" -- ValueError otherwise); None: "compact" if the environment has TRUSS_OBS_LAYOUT=compact,
+    else "dense".  Both play the same game, bit for bit; the update reads dense samples either way.
     level_backward: how the update differentiates a level of GCN layers on the GPU -- "library" (batched library GEMMs, the
     default) or "hip" (one `truss_gcn_level_backward` launch per level); None: "hip" if the environment has
     TRUSS_LEVEL_BACKWARD=1, else "library".  The choice is installed process-wide for cuda tensors (like the level forward)
@@ -165,7 +170,7 @@ class BatchedMARL:
                  level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None,
                  archive_path: str | None = None, actor_path: str | None = None, actor_precision: str | None = None,
                  pair_path: str | None = None, level_adjacency: str | None = None, optimizer_path: str | None = None,
-                 critic_tail: str | None = None):
+                 critic_tail: str | None = None, obs_layout: str | None = None):
         if game not in ("train", "test"):
             raise ValueError(f"game must be 'train' or 'test', got {game!r}")
         if game == "test" and len(topo.sym_nodes) == 0:
@@ -195,7 +200,7 @@ class BatchedMARL:
             import truss2D_RL
             truss2D_RL.set_level_forward(level_forward(self.lib), "cuda")   # the update's forward passes: one launch per level
         self._options(level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision, level_adjacency,
-                      optimizer_path, critic_tail)
+                      optimizer_path, critic_tail, obs_layout)
         self._arch_spare = None       # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
         self._pair_dtab = self._pair_frac = None   # pair_path="hip": deg^-1/2 and n / P as the framework rounds them on this device
         #                                             (pair_dtab, pair_frac_tab; made at the first step)
@@ -240,7 +245,7 @@ class BatchedMARL:
         self.profile = None            # set to {} to accumulate synchronised wall time per segment (diagnostic)
 
     def _options(self, level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision, level_adjacency,
-                 optimizer_path=None, critic_tail=None):
+                 optimizer_path=None, critic_tail=None, obs_layout=None):
         # (see the class) argument, else environment, else default; then what the choice needs of the library and of max_front
         def lib_has(flag, what, entry):
             if not flag:
@@ -257,6 +262,17 @@ class BatchedMARL:
         if self.critic_tail == "hip":
             lib_has(self.lib.has_critic_tail, "critic_tail='hip'", "truss_critic_tail")
         self.replay_storage = _option("replay_storage", replay_storage, "TRUSS_REPLAY_STORAGE", ("dense", "compact"))
+        self.obs_layout = _option("obs_layout", obs_layout, "TRUSS_OBS_LAYOUT", ("dense", "compact"))
+        if self.obs_layout == "compact":
+            lib_has(self.lib.has_obs_compact, "obs_layout='compact'", "truss_topo_neighbors")
+            if self.game == "train" and self.replay_storage != "compact":
+                raise ValueError("obs_layout='compact' in the train game needs replay_storage='compact': a dense ring holds [N, N] adjacencies")
+            self.envP.obs_width("compact")                        # the library's table against the topology's, once, here
+        # what the layout adds to the calls that carry it; the dense engine calls everything exactly as it always did
+        compact = self.obs_layout == "compact"
+        self._kw_obs = dict(obs_layout="compact") if compact else {}
+        self._kw_act = dict(compact=True) if compact else {}
+        self._kw_add = dict(compact_in=True) if compact else {}
         self.reward_path = _option("reward_path", reward_path, "TRUSS_REWARD", ("torch", "hip"))
         if self.reward_path == "hip":
             lib_has(self.lib.has_reward, "reward_path='hip'", "truss_reward")
@@ -328,7 +344,7 @@ class BatchedMARL:
         graph: (x_p, A_p) of the same (pts0, n0, index) if the caller has them already (the candidates see their parent's front)"""
         k = env.B if k is None else k
         if o is None:
-            o = env.observe(n_active=k)
+            o = env.observe(n_active=k, **self._kw_obs)
         x_p, A_p = graph if graph is not None else pareto_graph(pts0, n0, index, self.P)
         if rep > 1:
             x_p, A_p = x_p.repeat(rep, 1, 1), A_p.repeat(rep, 1, 1)
@@ -359,11 +375,11 @@ class BatchedMARL:
             grouped = None
             if self.actor_path == "grouped":                          # every actor's layers of a depth in one launch, before any noise
                 grouped = actors_infer(self.lib, [ag.actor_model for ag in self.rl.agents], net_in, nbr=self.nbr, nbr_p=self.nbr_p,
-                                       precision=self.actor_precision)
+                                       precision=self.actor_precision, **self._kw_act)
             for i, ag in enumerate(self.rl.agents):
                 g, t = grouped[i] if grouped is not None else actor_infer(
                     self.lib, ag.actor_model, net_in, nbr=self.nbr, nbr_p=self.nbr_p, fused=self.actor_path == "fused",
-                    precision=self.actor_precision)
+                    precision=self.actor_precision, **self._kw_act)
                 if explore:                                          # truss2D_RL.OUNoise.gen_noise per scalar (:41-48), all columns at once
                     for out, noises in ((g, ag.noise_geo), (t, ag.noise_topo)):
                         th_dt, mu, sg = self._noise_vectors(noises)
@@ -562,7 +578,7 @@ class BatchedMARL:
         # parents: the members of the step-start archive (:211-221)
         eP.x[:K], eP.target[:K], eP.env_params[:K] = cx, ct, cp
         eP.y[:K], eP.sec[:K] = py, ps
-        S = self._obs(eP, p0, nn0, ms, k=K, o=eP.analyze(n_active=K, obs=True))          # analysis + observations: one launch
+        S = self._obs(eP, p0, nn0, ms, k=K, o=eP.analyze(n_active=K, obs=True, **self._kw_obs))          # analysis + observations: one launch
         # the three agents modify the SAME parent (:249-260)
         eC.x[:3 * K], eC.target[:3 * K], eC.env_params[:3 * K] = cx.repeat(3, 1), ct.repeat(3, 1), cp.repeat(3, 1)
         eC.y[:3 * K], eC.sec[:3 * K] = py.repeat(3, 1), ps.repeat(3, 1)
@@ -579,7 +595,7 @@ class BatchedMARL:
         pq = pair_setup(self.lib, idx, ms, start["pts"], start["n"], start["y"], start["sec"], self.c_x, self.c_target, self.c_params,
                         self.ref_points, rep=1 if test else 3, dtab=self._pair_dtab, frac_tab=self._pair_frac, par=env_rows(eP), cand=env_rows(eC),
                         coins=(self.seed, self.env_ids, self.game_step) if test else None)
-        pq["S"] = self._obs(eP, pq["p0"], pq["nn0"], ms, k=K, o=eP.analyze(n_active=K, obs=True), graph=(pq["x_p"][:K], pq["A_p"][:K]))
+        pq["S"] = self._obs(eP, pq["p0"], pq["nn0"], ms, k=K, o=eP.analyze(n_active=K, obs=True, **self._kw_obs), graph=(pq["x_p"][:K], pq["A_p"][:K]))
         pq["ark"] = torch.arange(K, device=self.device) if self.archive_path == "hip" and not test else None    # (for the merge's table of rows)
         return pq
 
@@ -588,7 +604,7 @@ class BatchedMARL:
         game observes nothing, it has no replay).  Returns the clamped actions (they go to the replay, :375) and the next states."""
         eC = self.envC
         a_geo, a_topo = torch.cat(geo, 0).contiguous(), torch.cat(topo, 0).contiguous()
-        oC = eC.step(a_geo, a_topo, pq["coin"], clamp_inplace=True, n_active=3 * K, obs=not test)
+        oC = eC.step(a_geo, a_topo, pq["coin"], clamp_inplace=True, n_active=3 * K, obs=not test, **self._kw_obs)
         self._steps_dev += 3 * K
         # the candidates see their parent's front: its Pareto graph, repeated per agent unless the set-up wrote the copies
         return a_geo, a_topo, None if test else self._obs(eC, pq["p0"], pq["nn0"], ms, rep=3 * K // pq["x_p"].shape[0], k=3 * K, o=oC,
@@ -654,7 +670,7 @@ class BatchedMARL:
         NSv = {k: NSall[k].view(3, K, *NSall[k].shape[1:]) for k in DeviceReplay.KEYS}
         ag = a_geo.view(3, K, -1, 2).permute(1, 0, 2, 3)
         at = a_topo.view(3, K, -1, 3).permute(1, 0, 2, 3)
-        return self.replay.add(accepted.any(dim=1), S, NSv, ag, at, R.float(), src=src)
+        return self.replay.add(accepted.any(dim=1), S, NSv, ag, at, R.float(), src=src, **self._kw_add)
 
     def _cull(self, candP, candY, candS, max_front):
         """The torch cull: the front of the archive (P rows, dead rows marked infeasible) + C candidate slots, truncated to

@@ -23,10 +23,15 @@ class DeviceReplay:
     On a cuda device with a native library that exports them, compact storage moves every field of a transition with ONE
     `replay_scatter` launch per `add` and ONE `replay_gather` launch per `sample` (csrc/truss_replay.h); on the cpu, or without the
     entries, the same semantics run as framework indexing (gather through the table on add, zeros + scatter on sample).
-    fused=True does the same for dense storage (plain copies only); it needs the operators."""
+    fused=True does the same for dense storage (plain copies only); it needs the operators.
+    `add(..., compact_in=True)` (compact storage only): the node-graph adjacencies of S / NS arrive in the compact observation layout
+    already -- [.., N, Kn] rows of the same table, as the step / observation kernels write them with TRUSS_F_OBS_COMPACT -- and travel
+    as plain fields, a row copy each; A_p is dense on the way in as ever.  The rings hold the same bits as after a dense-in add of
+    the same transitions."""
 
     KEYS = ("x_n", "A_s", "A_n_ts", "A_n_cs", "x_p", "A_p")
     PATTERN_KEYS = ("A_s", "A_n_ts", "A_n_cs", "A_p")
+    NODE_GRAPH_KEYS = ("A_s", "A_n_ts", "A_n_cs")             # what compact_in covers
 
     def __init__(self, capacity, N, P, device, storage="dense", nbr=None, nbr_p=None, lib=None, fused=False):
         if storage not in ("dense", "compact"):
@@ -61,6 +66,8 @@ class DeviceReplay:
             self._fields = [(self.S[k], k, 0) for k in self.KEYS] + [(self.NS[a][k], k, 1 + a) for a in range(3) for k in self.KEYS]
             self._rings = [t for t, _, _ in self._fields] + [self.a_geo, self.a_topo, self.R]
             self._nbrs = [self._tab[k][0] if k in self._tab else None for _, k, _ in self._fields] + [None, None, None]
+            # compact-in rows of the node-graph adjacencies are plain fields: no table for them
+            self._nbrs_cin = [None if k in self.NODE_GRAPH_KEYS else n for (_, k, _), n in zip(self._fields, self._nbrs)] + [None, None, None]
             self._groups = [g for _, _, g in self._fields] + [0, 0, 0]
 
     @staticmethod
@@ -79,9 +86,10 @@ class DeviceReplay:
         ts = list(self.S.values()) + [t for ns in self.NS for t in ns.values()] + [self.a_geo, self.a_topo, self.R]
         return sum(t.numel() * t.element_size() for t in ts)
 
-    def _put(self, ring, key, pos, rows):
-        """ring[pos] = rows (dense tensors [k, ...]); a pattern key of compact storage keeps the table's entries only"""
-        if key in self._tab:
+    def _put(self, ring, key, pos, rows, compact_in=False):
+        """ring[pos] = rows (dense tensors [k, ...]); a pattern key of compact storage keeps the table's entries only -- unless the
+        rows are compact already (compact_in, node-graph adjacencies): a plain row copy"""
+        if key in self._tab and not (compact_in and key in self.NODE_GRAPH_KEYS):
             _, slot, cols = self._tab[key]
             ring.view(self.capacity, -1)[pos[:, None], slot[None, :]] = rows.reshape(rows.shape[0], -1)[:, cols]
         else:
@@ -95,12 +103,21 @@ class DeviceReplay:
             return out
         return ring[i]
 
-    def add(self, sel, S, NS, a_geo, a_topo, R, src=None):
+    def add(self, sel, S, NS, a_geo, a_topo, R, src=None, compact_in=False):
         """append the transitions of the rows where sel[K] is True.  NS: three dicts (one per agent's next state), or -- with src
         [K, 3] -- ONE dict of tensors [3, K, ...] from which agent a's next state of row r is taken at [src[r, a], r].
         With the fused operators the sources are read in place, the accepted rows only, when they are float32 and strided over their
         first two dims at most (the [3, K, ...] tensors of the `src` form: contiguous); other layouts are copied whole first
-        (`_rows_view`, and the `reshape` of a non-contiguous [3, K, ...] tensor)."""
+        (`_rows_view`, and the `reshape` of a non-contiguous [3, K, ...] tensor).
+        compact_in: A_s / A_n_ts / A_n_cs of S and NS are [.., N, Kn] rows of the table already (see the class)."""
+        if compact_in:
+            if self.storage != "compact":
+                raise ValueError("compact_in needs storage='compact': a dense ring holds [N, N] adjacencies")
+            for key in self.NODE_GRAPH_KEYS:
+                want = tuple(self.S[key].shape[1:])
+                for t in [S[key]] + ([NS[key]] if src is not None else [ns[key] for ns in NS]):
+                    if tuple(t.shape[-2:]) != want:
+                        raise ValueError(f"compact_in: {key} must end in {want}, got {tuple(t.shape)}")
         idx = torch.nonzero(sel, as_tuple=False).flatten()
         k = int(idx.numel())
         if k == 0:
@@ -108,15 +125,15 @@ class DeviceReplay:
         if k > self.capacity:
             idx, k = idx[: self.capacity], self.capacity
         if self._lib is not None:
-            self._add_fused(idx, k, S, NS, a_geo, a_topo, R, src)
+            self._add_fused(idx, k, S, NS, a_geo, a_topo, R, src, compact_in)
         else:
             pos = (self.head + torch.arange(k, device=idx.device)) % self.capacity
             pick = None if src is None else src[idx]                               # [k, 3]
             if self._tab:
                 for key in self.KEYS:
-                    self._put(self.S[key], key, pos, S[key][idx])
+                    self._put(self.S[key], key, pos, S[key][idx], compact_in)
                     for a in range(3):
-                        self._put(self.NS[a][key], key, pos, NS[a][key][idx] if src is None else NS[key][pick[:, a], idx])
+                        self._put(self.NS[a][key], key, pos, NS[a][key][idx] if src is None else NS[key][pick[:, a], idx], compact_in)
             else:
                 for key in self.KEYS:
                     self.S[key][pos] = S[key][idx]
@@ -136,7 +153,7 @@ class DeviceReplay:
         inner = lambda d0: all(t.shape[d] == 1 or t.stride(d) == int(np.prod(t.shape[d + 1:])) for d in range(d0, t.dim()))
         return t if inner(1) or (t.dim() >= 2 and inner(2) and t.stride(1) >= 0 and t.stride(0) >= 0) else t.contiguous()
 
-    def _add_fused(self, idx, k, S, NS, a_geo, a_topo, R, src):
+    def _add_fused(self, idx, k, S, NS, a_geo, a_topo, R, src, compact_in=False):
         K = S[self.KEYS[0]].shape[0]
         if src is None:
             rows = idx[None, :].expand(4, k).contiguous()
@@ -148,8 +165,8 @@ class DeviceReplay:
             nxt = lambda a, key: flat[key]
         srcs = [S[key] for key in self.KEYS] + [nxt(a, key) for a in range(3) for key in self.KEYS] + [a_geo, a_topo, R]
         srcs = [self._rows_view(t) for t in srcs]
-        ops.call(ops.namespace().replay_scatter, ops.bind(self._lib), ops.stream_of(self.R.device), self._rings, srcs, self._nbrs, self._groups,
-                 rows, k, self.head, self.capacity)
+        ops.call(ops.namespace().replay_scatter, ops.bind(self._lib), ops.stream_of(self.R.device), self._rings, srcs,
+                 self._nbrs_cin if compact_in else self._nbrs, self._groups, rows, k, self.head, self.capacity)
 
     def sample(self, batch, generator=None):
         i = torch.randint(0, self.size, (batch,), device=self.R.device, generator=generator)

@@ -128,6 +128,17 @@ class TrussTopology:
                                                  C.byref(g), C.byref(rpl)), "truss_topo_solver_info")
         return dict(perm=perm, half_bandwidth=bw.value, lanes_per_env=g.value, rows_per_lane=rpl.value)
 
+    def native_neighbors(self, lib):
+        """The neighbour table the native library built for this topology (truss_topo_neighbors): int16 [N, Kc], the table
+        of its compact observation layout.  TrussError on a library without the entry."""
+        if not lib.has_obs_compact:
+            raise _lib.TrussError("the bound native library has no truss_topo_neighbors")
+        h, k = self.native(lib), C.c_int32()
+        lib.check(lib.dll.truss_topo_neighbors(h, None, 0, C.byref(k)), "truss_topo_neighbors")
+        tab = np.zeros((self.N, k.value), np.int16)
+        lib.check(lib.dll.truss_topo_neighbors(h, tab.ctypes.data_as(C.c_void_p), tab.size, C.byref(k)), "truss_topo_neighbors")
+        return tab
+
     def close(self):
         for lib, h in self._native.values():
             lib.dll.truss_topo_destroy(h)
