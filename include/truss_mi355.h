@@ -843,6 +843,42 @@ typedef struct truss_critic_tail_bwd {
 int truss_critic_tail(const truss_critic_tail_args_t *items, int32_t n_items, void *stream);
 int truss_critic_tail_backward(const truss_critic_tail_bwd_t *items, int32_t n_items, void *stream);
 
+/* ---- target update: the target networks of the MADDPG update follow their online networks, gated on the device ------------
+ * replaces: nothing that runs today -- the reference's soft update never fires (truss2D_RL.py:392-400, :692-699) and the default of
+ * this project keeps that; MADDPG(target_update="polyak" / "hard") asks for targets that track, and this is their native path.
+ * One call moves n_pairs target tensors t towards their source tensors p, all float32, u = 2^-24, per element, with the two
+ * branches of torch.lerp (the product may or may not be contracted into an FMA):
+ *   tau < 0.5        t' = t + (float) tau (p - t)
+ *   0.5 <= tau < 1   t' = p - (p - t) (float) (1 - tau)
+ *   tau == 1         t' = p, a copy of the bits
+ * The gate: with step != NULL the call changes something iff fmod(*step, (double) period) == 0, where *step is read ON THE DEVICE
+ * by every workgroup before its first store -- one captured call fires on some replays and not on others.  A gate that does not
+ * fire stores nothing.  step == NULL: always fires.
+ * One 256-thread workgroup per chunk of TRUSS_TARGET_CHUNK elements of a pair, one launch per TRUSS_TARGET_MAX_PAIRS pairs (longer
+ * lists run as consecutive launches).  16-byte accesses where both addresses of the chunk are 16-byte aligned and its length is a
+ * multiple of 4, word by word otherwise, the same elements either way.  The descriptors travel in the kernel arguments: the entry
+ * allocates nothing and does not synchronise; capturable.  Every element has one owner (no atomics).
+ *   pairs  HOST array [n_pairs]: t, p device pointers (contiguous), numel 1..2^31-1        step  device double, or NULL
+ * TRUSS_EINVAL, with nothing launched or written: bad struct_size, n_pairs < 0, NULL pairs with n_pairs > 0, a NULL t or p, numel
+ * outside 1..2^31-1, tau not in (0, 1], period < 1, a target range overlapping a source range or another target range.
+ * n_pairs == 0: TRUSS_OK, no launch.  Optional entry of ABI version 3 (a library may lack it). */
+#define TRUSS_TARGET_CHUNK 4096        /* elements per workgroup */
+#define TRUSS_TARGET_MAX_PAIRS 160     /* pairs per launch */
+typedef struct truss_target_pair {
+  float *t;
+  const float *p;
+  int64_t numel;
+} truss_target_pair_t;
+typedef struct truss_target_args {
+  size_t struct_size;
+  int32_t n_pairs;
+  const truss_target_pair_t *pairs;
+  double tau;
+  int64_t period;
+  const double *step;            /* NULL: always fires */
+} truss_target_args_t;
+int truss_target_update(const truss_target_args_t *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

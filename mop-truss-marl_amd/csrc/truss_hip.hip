@@ -11,7 +11,7 @@
 // (Pareto front + hypervolume), truss_reward.h (the difference reward), truss_archive.h (the archive update),
 // truss_pairs.h (the set-up of a chunk of pairs), truss_gcn_aggregate.h and truss_gcn_level_agg.h (a level's neighbour sums
 // through the node table), truss_optim.h (clip and Adam of the MADDPG update), truss_critic_tail.h (pools and dense layers of a
-// critic pass of the update, forward and backward).
+// critic pass of the update, forward and backward), truss_target.h (the target networks follow the online ones).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -558,3 +558,4 @@ extern "C" int truss_debug_stamps(unsigned long long *out16) {
 #include "truss_gcn_level_agg.h"
 #include "truss_optim.h"
 #include "truss_critic_tail.h"
+#include "truss_target.h"

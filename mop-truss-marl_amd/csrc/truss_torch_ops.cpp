@@ -46,7 +46,8 @@
   X(gcn_level_aggregate, truss_gcn_level_aggregate, false)        \
   X(optim_step, truss_optim_step, false)                         \
   X(critic_tail, truss_critic_tail, false)                       \
-  X(critic_tail_backward, truss_critic_tail_backward, false)
+  X(critic_tail_backward, truss_critic_tail_backward, false)     \
+  X(target_update, truss_target_update, false)
 #define TRUSS_ENTRY_POINTS(X) TRUSS_OPERATOR_ENTRIES(X) X(last_error, truss_last_error, true)
 
 namespace {
@@ -574,6 +575,39 @@ void optim_step(int64_t lib, int64_t stream, int64_t mode, at::TensorList params
   check_rc(b, b.optim_step(&a, (void *)stream), "truss_optim_step");
 }
 
+// targets[i] (contiguous float32, updated in place) follows sources[i] (as many elements, not modified): lerp(target, source, tau)
+// where *step mod period == 0 -- `step` a float64 tensor read on the device; None: always -- nothing written otherwise
+// == truss_target_update
+void target_update(int64_t lib, int64_t stream, at::TensorList targets, at::TensorList sources, double tau, int64_t period, const OT &step) {
+  const Backend &b = backend(lib);
+  need(b.target_update, "truss_target_update");
+  const size_t L = targets.size();
+  TORCH_CHECK(sources.size() == L, "truss_mi355: target_update: ", L, " targets, ", sources.size(), " sources");
+  TORCH_CHECK(L <= (size_t)INT32_MAX, "truss_mi355: target_update: too many tensors");
+  std::vector<truss_target_pair_t> ps(L);
+  // `ptr` with the tensor's index in its name; the name is only built for a tensor that `ptr` will refuse
+  auto at_ptr = [&](const at::Tensor &t, const char *list, size_t i) {
+    if (t.scalar_type() == at::kFloat && t.is_contiguous() && (b.device ? t.is_cuda() : t.is_cpu()) && t.numel() >= 1) return (float *)t.data_ptr();
+    const std::string name = std::string(list) + "[" + std::to_string(i) + "]";
+    return ptr<float>(b, t, at::kFloat, name.c_str(), 1);
+  };
+  for (size_t i = 0; i < L; ++i) {
+    ps[i].t = at_ptr(targets[i], "targets", i);
+    ps[i].p = at_ptr(sources[i], "sources", i);
+    ps[i].numel = targets[i].numel();
+    TORCH_CHECK(sources[i].numel() == ps[i].numel, "truss_mi355: target_update: targets[", i, "] has ", ps[i].numel, " elements, sources[", i,
+                "] ", sources[i].numel());
+  }
+  truss_target_args_t a{};
+  a.struct_size = sizeof(truss_target_args_t);
+  a.n_pairs = (int32_t)L;
+  a.pairs = ps.data();
+  a.tau = tau;
+  a.period = period;
+  a.step = ptr<const double>(b, step, at::kDouble, "step", 1);
+  check_rc(b, b.target_update(&a, (void *)stream), "truss_target_update");
+}
+
 // the tails of several critic passes (items) in one call: item j pools its n_layers[j] level outputs o [B, N, H] -- the lists of all
 // items one after the other in `o` -- over the nodes, concatenates them and applies relu(w1 . + b1) [Q, L H], relu(w2 . + b2) [Q, Q],
 // w3 . + b3 [1, Q] -> q[j] [B, 1]; p / z1 / z2: empty lists, or per item None or the tensors [B, L H], [B, Q], [B, Q] the backward
@@ -1077,6 +1111,7 @@ TORCH_LIBRARY(truss_mi355, m) {
   m.def("critic_tail_backward(int lib, int stream, int[] n_layers, int[] n_nodes, Tensor[] dq, Tensor?[] p, Tensor[] z1, Tensor[] z2, Tensor[] w1, "
         "Tensor[] w2, Tensor[] w3, Tensor?[] o, Tensor(a!)?[] d_o, Tensor(b!)?[] dz1, Tensor(c!)?[] dz2, Tensor(d!)?[] d_w1, Tensor(e!)?[] d_b1, "
         "Tensor(f!)?[] d_w2, Tensor(g!)?[] d_b2, Tensor(h!)?[] d_w3, Tensor(i!)?[] d_b3) -> ()");
+  m.def("target_update(int lib, int stream, Tensor(a!)[] targets, Tensor[] sources, float tau, int period, Tensor? step) -> ()");
 }
 static void register_operators(torch::Library &m) {
 #define X(field, symbol, required) m.impl(#field, field);

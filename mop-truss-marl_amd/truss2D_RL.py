@@ -15,7 +15,9 @@ Quirks of the reference that are kept on purpose:
     branch of the TD target never fires (:605-611); the target averages the three next-state Qs;
   * the actor is stepped by a FRESH Adam(lr*0.1, clipnorm=1) every call (:629);
   * `OneAgent.update()` acts only when update_num == 1000, `MADDPG.update()` calls it only when
-    agents[0].update_num % 300 == 0 -> the targets keep their initial hard copy (:392-400, :692-699).
+    agents[0].update_num % 300 == 0 -> the targets keep their initial hard copy (:392-400, :692-699).  Kept by default;
+    `MADDPG(target_update="polyak" / "hard")` tracks: the targets then move at the end of every `train_on_batch`
+    (`set_target_update`, `_target_update_torch`), the reference-named `update()` methods keep the quirk.
 
 Multi-GPU: pass `dist=torch.distributed` (backend "nccl" = RCCL on MI355X): every optimiser step is
 preceded by ONE all-reduce of the flat gradient buffer; the env batch itself needs
@@ -187,6 +189,21 @@ def set_optimizer_step(fn, device_type="cuda"):
         _OPTIMIZER_STEP.pop(device_type, None)
     else:
         _OPTIMIZER_STEP[device_type] = fn
+
+
+_TARGET_UPDATE = {}        # device type -> callable(targets, sources, tau, period, step) (truss_mi355.target.target_hook)
+
+
+def set_target_update(fn, device_type="cuda"):
+    """Install (or, with None, remove) the fused target update of `MADDPG.train_on_batch` for parameters on `device_type` (it runs only
+    with `MADDPG(target_update="polyak" / "hard")`).  One call `fn(targets, sources, tau, period, step)` takes the place of
+    `_target_update_torch`: targets / sources are lists of contiguous float32 tensors that pair up by position, step the 0-dim float64
+    step counter of the critics' optimiser (already incremented); where `step mod period == 0` -- decided on the device -- every
+    target becomes lerp(target, source, tau) in place, otherwise nothing is written."""
+    if fn is None:
+        _TARGET_UPDATE.pop(device_type, None)
+    else:
+        _TARGET_UPDATE[device_type] = fn
 
 
 _CRITIC_TAIL = {}          # device type -> hook with .forward(items, save) and .backward(items, states, dqs, needs) (truss_mi355.critic_tail)
@@ -792,6 +809,27 @@ def _fresh_adam_step(params, lr, eps, flat_grad=None):
         torch._foreach_add_(ps, upd, alpha=-lr)
 
 
+@torch.no_grad()
+def _target_update_torch(targets, sources, tau, period, step):
+    """The target update by framework operators (the contract of a `set_target_update` hook): a fixed number of multi-tensor
+    operations whatever the number of tensors (two concatenations, the lerp, the gate, one multi-tensor copy: 11 launches for the 222 tensors of
+    three actors and three critics, 14 with a gate), capturable, no host synchronisation.  The two branches of `torch.lerp`, float32 per element:
+    tau < 0.5: t + (float) tau (p - t); 0.5 <= tau < 1: p - (p - t) (float) (1 - tau); tau == 1: p.  The gate is a 0-dim bool on the
+    device (`step mod period == 0`) that selects between the new values and the old bits; period 1 needs none.  A gate that does
+    not fire therefore still pays the whole traffic and writes every target back as it was: branching on it would need the host."""
+    t = torch.cat([x.reshape(-1) for x in targets])
+    p = torch.cat([x.reshape(-1) for x in sources])
+    if tau == 1.0:
+        new = p
+    elif tau < 0.5:
+        new = (p - t).mul_(tau).add_(t)                  # (a Python scalar meets float32 elements as a float32)
+    else:
+        new = torch.sub(p, (p - t).mul_(1.0 - tau))
+    if step is not None and period != 1:
+        new = torch.where(torch.remainder(step, float(period)) == 0, new, t)
+    torch._foreach_copy_(list(targets), [n.view_as(x) for n, x in zip(new.split([x.numel() for x in targets]), targets)])
+
+
 def _allreduce_flat(flat, dist):
     """all-reduce (mean over ranks) of an already flat gradient vector, in place"""
     if dist is None or not dist.is_initialized():
@@ -872,7 +910,14 @@ class multimodals_OneAgent:
 
 class MADDPG:
     def __init__(self, lr, ep, epd, gamma, a_nn, c_nn, max_mem, num_agents, num_action, mu, theta, sigma,
-                 max_poss_n_num=1, device="cpu", dist=None):
+                 max_poss_n_num=1, device="cpu", dist=None, *, target_update=None, target_tau=None, target_period=None):
+        """target_update: None / "fixed" (the default: the reference's behaviour, the targets keep their initial hard copy and
+        `train_on_batch` never touches them), "polyak" (every `target_period`-th update, default every one, each target network
+        becomes t + tau (p - t) of its online network p; tau = `target_tau`, default `OneAgent.tau` = 0.005, in (0, 1]) or "hard"
+        (every `target_period`-th update t = p; `target_period` is required).  The update happens once per `train_on_batch`, behind
+        the third actor step; "every k-th" counts the shared critics' Adam steps (`critics_opt.step_t`), on the device.  One set
+        of agents over several engines (`MixedMARL`): every class's update is a `train_on_batch` call, so the targets move once per
+        update of any class, on the one shared counter."""
         self.num_agents = num_agents
         self.lr, self.epint, self.ep, self.epd, self.epmin, self.gamma = lr, ep, ep, epd, 0.05, gamma
         self.a_nn, self.c_nn = a_nn, c_nn
@@ -889,6 +934,22 @@ class MADDPG:
         self.dist = dist
         self.critics_opt = None      # one SharedStepAdam over the three critics, created once the lazy layers are materialised
         self.gen_agents()
+        self.target_update = "fixed" if target_update is None else target_update
+        if self.target_update not in ("fixed", "polyak", "hard"):
+            raise ValueError(f"target_update must be None, 'fixed', 'polyak' or 'hard', got {target_update!r}")
+        if target_tau is not None and not 0.0 < float(target_tau) <= 1.0:
+            raise ValueError(f"target_tau must be in (0, 1], got {target_tau!r}")
+        if target_period is not None and (int(target_period) != target_period or target_period < 1):
+            raise ValueError(f"target_period must be an integer >= 1, got {target_period!r}")
+        if self.target_update == "hard":
+            if target_period is None:
+                raise ValueError("target_update='hard' needs target_period (updates between two copies): there is no default")
+            if target_tau is not None and float(target_tau) != 1.0:
+                raise ValueError("target_update='hard' copies (tau = 1): target_tau does not apply")
+            self.target_tau = 1.0
+        else:
+            self.target_tau = float(self.agents[0].tau if target_tau is None else target_tau)
+        self.target_period = 1 if target_period is None else int(target_period)
 
     def gen_agents(self):
         for i in range(3):       # the reference builds exactly three agents (:438-452)
@@ -1020,6 +1081,20 @@ class MADDPG:
             # agent i's weights have just changed: an evaluation of actor i taken before this step must not be reused (the others'
             # stay valid: agents > i have not stepped yet, evaluations of agents < i were taken after their steps)
             frozen = {j: v for j, v in frozen.items() if j != i}
+        if self.target_update != "fixed":
+            # Data-parallel: no collective.  After the all-reduced steps above every rank holds the same online weights, and the
+            # same targets (`sync_parameters`); every rank applies the same map, gated by the same step counter.
+            self._update_targets()
+
+    @torch.no_grad()
+    def _update_targets(self):
+        """all six target networks follow the online networks as this `train_on_batch` left them (tensors pair up by `parameters()`
+        order), if `critics_opt.step_t mod target_period == 0` -- read on the device, never on the host"""
+        nets = [(ag.actor_model, ag.target_actor_model) for ag in self.agents] + [(ag.critic_model, ag.target_critic_model) for ag in self.agents]
+        sources = [p.detach() for src, _ in nets for p in src.parameters()]
+        targets = [p.detach() for _, dst in nets for p in dst.parameters()]
+        hook = _TARGET_UPDATE.get(self.device.type)                  # (`set_target_update`)
+        (hook or _target_update_torch)(targets, sources, self.target_tau, self.target_period, self.critics_opt.step_t)
 
     def sync_parameters(self, src=0):
         """Data-parallel start: every rank takes rank `src`'s actor / critic / target weights (one broadcast
@@ -1054,8 +1129,10 @@ class MADDPG:
     # checkpoints (master_DDPG_truss2D_MO.py:710-733, 885-906 use Keras save/load_weights)
     def save_weights(self, prefix):
         for i, ag in enumerate(self.agents):
-            torch.save({"actor": ag.actor_model.state_dict(), "critic": ag.critic_model.state_dict()},
-                       "{}Agent{}_pickle.pt".format(prefix, i + 1))
+            sd = {"actor": ag.actor_model.state_dict(), "critic": ag.critic_model.state_dict()}
+            if self.target_update != "fixed":        # tracking targets are state; in the default mode they are the online weights' start
+                sd.update(target_actor=ag.target_actor_model.state_dict(), target_critic=ag.target_critic_model.state_dict())
+            torch.save(sd, "{}Agent{}_pickle.pt".format(prefix, i + 1))
 
     def load_tf_actors(self, prefix):
         """Restore the actors (and target actors) from the reference's published TensorFlow checkpoints
@@ -1077,7 +1154,7 @@ class MADDPG:
         for i, ag in enumerate(self.agents):
             sd = torch.load("{}Agent{}_pickle.pt".format(prefix, i + 1), weights_only=True, map_location=self.device)
             ag.actor_model.load_state_dict(sd["actor"])
-            ag.target_actor_model.load_state_dict(sd["actor"])
+            ag.target_actor_model.load_state_dict(sd.get("target_actor", sd["actor"]))     # (a file of the default mode has no targets)
             ag.critic_model.load_state_dict(sd["critic"])
-            ag.target_critic_model.load_state_dict(sd["critic"])
+            ag.target_critic_model.load_state_dict(sd.get("target_critic", sd["critic"]))
             ag._targets_ready = True

@@ -133,6 +133,19 @@ class CriticTailBwd(C.Structure):
     ]
 
 
+class TargetPair(C.Structure):
+    _fields_ = [("t", _vp), ("p", _vp), ("numel", C.c_int64)]
+
+
+class TargetArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("n_pairs", C.c_int32), ("pairs", C.POINTER(TargetPair)), ("tau", C.c_double),
+                ("period", C.c_int64), ("step", _vp)]
+
+
+TARGET_CHUNK = 4096                   # truss_target_update: elements per workgroup
+TARGET_MAX_PAIRS = 160                # ... pairs per launch
+
+
 CRITIC_TAIL_MAX = 4                   # truss_critic_tail: items per launch
 CRITIC_TAIL_MAX_LAYERS = 16           # ... the envelope: layers, channels, dense units, concatenated length
 CRITIC_TAIL_MAX_HIDDEN = CRITIC_TAIL_MAX_Q = 256
@@ -181,6 +194,7 @@ _LATER_ENTRIES = [
     ("truss_optim_step", [C.POINTER(OptimArgs), _vp]),
     ("truss_topo_lds_info", [_vp, _i32, _vp, _vp, _i32, _vp, _i32]),
     ("truss_topo_neighbors", [_vp, _vp, _i32, C.POINTER(_i32)]),
+    ("truss_target_update", [C.POINTER(TargetArgs), _vp]),
     ("truss_critic_tail", [C.POINTER(CriticTailArgs), _i32, _vp]),
     ("truss_critic_tail_backward", [C.POINTER(CriticTailBwd), _i32, _vp]),
 ]
@@ -223,6 +237,7 @@ class TrussLib:
         self.has_level_aggregate = "truss_gcn_level_aggregate" in found                      # a level's neighbour sums through the node table
         self.has_optim_step = "truss_optim_step" in found                                    # clip and Adam of the update as one call
         self.has_critic_tail = {"truss_critic_tail", "truss_critic_tail_backward"} <= found  # pools and dense layers of a critic pass
+        self.has_target_update = "truss_target_update" in found                              # the target networks follow the online ones
         self.has_obs_compact = "truss_topo_neighbors" in found                               # the compact observation layout (F_OBS_COMPACT)
         if d.truss_abi_version() != TRUSS_ABI_VERSION:
             raise TrussError(f"{path}: ABI version {d.truss_abi_version()} != {TRUSS_ABI_VERSION}")

@@ -59,6 +59,7 @@ from .gcn import (PRECISIONS, actor_infer, actors_infer, gcn_aggregate, gcn_laye
                   level_aggregate, level_backward, level_forward, refresh_actor_caches, split_weights)
 from .critic_tail import tail_hook
 from .optim import optimizer_step
+from .target import target_hook
 from .pairs import design_coins, pair_dtab, pair_frac_tab, pair_setup, pareto_graph, path_graph_table  # noqa: F401
 from .replay import DeviceReplay
 from .topology import TrussTopology
@@ -162,7 +163,14 @@ class BatchedMARL:
     three dense layers; nine passes per update) -- "torch" (framework operators and autograd, the default) or "hip" (`truss_critic_tail`
     / `truss_critic_tail_backward`: one launch forward for all critics that run together, two backward, `critic_tail.tail_hook`; needs
     a library with those entries); None: "hip" if the environment has TRUSS_CRITIC_TAIL=hip, else "torch".  Installed process-wide for
-    cuda tensors like optimizer_path, and removed again by an engine built with "torch"."""
+    cuda tensors like optimizer_path, and removed again by an engine built with "torch".
+    target_path: how the update moves the target networks where the MADDPG asks for it (`MADDPG(target_update="polyak" / "hard")`: the
+    mode, tau and period are the MADDPG's, the engine only chooses the path; with the default mode no path runs) -- "torch"
+    (`truss2D_RL._target_update_torch`: a fixed number of multi-tensor operations, the default) or "hip" (one `truss_target_update` call,
+    two launches for the 222 parameter tensors: `target.target_hook`; needs a library with that entry); None: "hip" if the
+    environment has TRUSS_TARGET_PATH=hip, else "torch".  Either way the gate "every k-th update" is decided on the device, so one
+    captured update fires on some replays and not on others.  Installed process-wide for cuda tensors like optimizer_path, and
+    removed again by an engine built with "torch"."""
 
     def __init__(self, topo: TrussTopology, n_envs: int, maddpg, *, max_front: int | None = None, lib=None, device=None,
                  replay_capacity: int = 32768, batch_size: int = 32, hv_margin: float = 0.2, seed: int = 0,
@@ -170,7 +178,7 @@ class BatchedMARL:
                  level_backward: str | None = None, replay_storage: str | None = None, reward_path: str | None = None,
                  archive_path: str | None = None, actor_path: str | None = None, actor_precision: str | None = None,
                  pair_path: str | None = None, level_adjacency: str | None = None, optimizer_path: str | None = None,
-                 critic_tail: str | None = None, obs_layout: str | None = None):
+                 critic_tail: str | None = None, obs_layout: str | None = None, target_path: str | None = None):
         if game not in ("train", "test"):
             raise ValueError(f"game must be 'train' or 'test', got {game!r}")
         if game == "test" and len(topo.sym_nodes) == 0:
@@ -200,7 +208,7 @@ class BatchedMARL:
             import truss2D_RL
             truss2D_RL.set_level_forward(level_forward(self.lib), "cuda")   # the update's forward passes: one launch per level
         self._options(level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision, level_adjacency,
-                      optimizer_path, critic_tail, obs_layout)
+                      optimizer_path, critic_tail, obs_layout, target_path)
         self._arch_spare = None       # archive_path="hip": the set of archive buffers the next merge writes (see _merge_archive)
         self._pair_dtab = self._pair_frac = None   # pair_path="hip": deg^-1/2 and n / P as the framework rounds them on this device
         #                                             (pair_dtab, pair_frac_tab; made at the first step)
@@ -209,6 +217,7 @@ class BatchedMARL:
             truss2D_RL.set_level_backward(_level_backward_hook(self.lib) if self.level_backward == "hip" else None, "cuda")
             truss2D_RL.set_optimizer_step(optimizer_step(self.lib) if self.optimizer_path == "hip" else None, "cuda")
             truss2D_RL.set_critic_tail(tail_hook(self.lib) if self.critic_tail == "hip" else None, "cuda")
+            truss2D_RL.set_target_update(target_hook(self.lib) if self.target_path == "hip" else None, "cuda")
         # level_adjacency="table": the node table of this truss, current during every update of this engine (`_train`); the table's
         # device tensor stays with the pattern, i.e. with the engine: a captured update holds its address
         self.pattern = None
@@ -245,7 +254,7 @@ class BatchedMARL:
         self.profile = None            # set to {} to accumulate synchronised wall time per segment (diagnostic)
 
     def _options(self, level_backward, replay_storage, reward_path, archive_path, pair_path, actor_path, actor_precision, level_adjacency,
-                 optimizer_path=None, critic_tail=None, obs_layout=None):
+                 optimizer_path=None, critic_tail=None, obs_layout=None, target_path=None):
         # (see the class) argument, else environment, else default; then what the choice needs of the library and of max_front
         def lib_has(flag, what, entry):
             if not flag:
@@ -261,6 +270,9 @@ class BatchedMARL:
         self.critic_tail = _option("critic_tail", critic_tail, "TRUSS_CRITIC_TAIL", ("torch", "hip"))
         if self.critic_tail == "hip":
             lib_has(self.lib.has_critic_tail, "critic_tail='hip'", "truss_critic_tail")
+        self.target_path = _option("target_path", target_path, "TRUSS_TARGET_PATH", ("torch", "hip"))
+        if self.target_path == "hip":
+            lib_has(self.lib.has_target_update, "target_path='hip'", "truss_target_update")
         self.replay_storage = _option("replay_storage", replay_storage, "TRUSS_REPLAY_STORAGE", ("dense", "compact"))
         self.obs_layout = _option("obs_layout", obs_layout, "TRUSS_OBS_LAYOUT", ("dense", "compact"))
         if self.obs_layout == "compact":
@@ -799,7 +811,9 @@ class MixedMARL:
     One `BatchedMARL` engine per size class -- archives, env objects and replay have the class's shapes -- all sharing
     `maddpg`.  Envs are dealt to ranks in buckets like `MixedTrussPool` (pool.deal_buckets): every rank plays the same
     class mix.  A game step plays every class; the updates of the step then draw their batches from the classes'
-    replays in turn (a batch is of one class: its tensors have that class's shapes)."""
+    replays in turn (a batch is of one class: its tensors have that class's shapes).
+    Tracking targets (`MADDPG(target_update=...)`) need nothing special here: each class's update is a `train_on_batch` call, so
+    the targets move once per update of any class, counted by the one shared step counter of the critics' optimiser."""
 
     def __init__(self, classes, maddpg, *, bucket_envs=64, rank=0, world=1, **engine_kw):
         """engine_kw go to every class's BatchedMARL (game="test": every class brings its own symmetric topology; the coin's env
